@@ -6,9 +6,11 @@ One "step" = one pass of the hot path over one batch of synthetic triplets alrea
   + heads forward -> TripletMarginLoss -> backward -> [RCCL all-reduce of the flat gradient arena] -> Adam.
 Workload = BASELINE.json configs[1]: Kuka + GoogleCommand shapes, per-GPU batch 256, fp32, weak scaling.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
-Rank 0 prints ONE JSON line."""
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints it; --full adds the roofline,
+per-kernel, CPU-baseline and CPU-parity legs.  --dump-outputs DIR writes what the last timed step computed (loss,
+parameters, gradients) as DIR/<name>.npy; the inputs and weights are seeded, so two builds compare output for output."""
 import argparse
 import json
 import math
@@ -210,9 +212,12 @@ def main_ithor(args, rank, local_rank, world, dev):
         for tag in range(len(names)):
             if "11x5" not in names[tag]:
                 continue
-            ctx.profile_select(tag)
-            for _ in range(3):
+            if args.full:
+                ctx.profile_select(tag)
+            for _ in range(3):                                  # (a plain run takes the same steps, unprofiled)
                 step()
+            if not args.full:
+                continue
             ms, n = ctx.profile_read()
             if n and (best is None or ms / n > best[1]):
                 best = (tag, ms / n, n)
@@ -279,7 +284,9 @@ def main_ithor(args, rank, local_rank, world, dev):
                 raise SystemExit("bench.py: a GRU hand-off wait expired (is another process using this GPU?)")
         if roof:
             out["roofline"] = roof
-        if not args.no_cpu_baseline and world == 1:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"loss": tr.loss, "params": model.flat_parameters(), "grads": tr.grads})
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = ithor_cpu_baseline()
         emit(json.dumps(out))
     if torch.distributed.is_initialized():
@@ -357,6 +364,22 @@ def algorithmic_bytes(tag, B, hw):
             }.get(tag)
 
 
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array the last timed step left for its caller as `path`/<name>.npy, float32 (called after the
+    timed region has been synchronised)."""
+    import numpy as np
+    host = {name: t.detach().float().cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 _REAL_STDOUT = None
 
 
@@ -430,8 +453,12 @@ def dry_run_cpu(args, rank, world):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 200; 20 for --workload ithor)")
+    ap.add_argument("--warmup", type=int, default=None, help="warm-up steps before them (default 20; 3 for --workload ithor)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, per-kernel, CPU-baseline and CPU-parity legs (a plain run times the step only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, parameters, gradients) as DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
@@ -461,6 +488,10 @@ def main():
     ap.add_argument("--pool", type=int, default=4096,
                     help="kuka workload: triplets in the HBM-resident synthetic pool (16384 = 1.4 GB > the 256 MB Infinity Cache)")
     args = ap.parse_args()
+    if args.workload == "ithor" and args.steps is None and args.warmup is None:
+        args.steps, args.warmup = 20, 3                         # the defaults below are sized for the 0.37 ms Kuka step
+    args.steps = 200 if args.steps is None else args.steps
+    args.warmup = 20 if args.warmup is None else args.warmup
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -493,8 +524,6 @@ def main():
     args.n_ranks_seen = torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1
 
     if args.workload == "ithor":
-        if args.steps == 200 and args.warmup == 20:           # the defaults are sized for the 0.37 ms Kuka step
-            args.steps, args.warmup = 20, 3
         return main_ithor(args, rank, local_rank, world, dev)
 
     import var_amd
@@ -572,11 +601,13 @@ def main():
     # pick the dominant conv kernel family by the kernel's OWN duration (three profiled eager steps per candidate with every
     # launch on one stream: what the rocprofv3 kernel-stats average reads too; beside the side stream's kernels the event
     # bracket of whichever kernel runs next to the MFCC reads longest, which says nothing about that kernel)
+    dom_tags, img_tags = list(range(0, 10)) + list(range(11, 15)), (1, 2, 12, 7, 11, 15)
+    legs = args.full and not args.no_roofline
     dom_tag = None
-    if not args.no_roofline:
+    if legs:
         best = -1.0
         sel_mask = ctx.set_streams(0)
-        for tag in list(range(0, 10)) + list(range(11, 15)):
+        for tag in dom_tags:
             ctx.profile_select(tag)
             for _ in range(3):
                 eager_step()
@@ -614,11 +645,10 @@ def main():
     # kernels take less than the second leg reads (eager launches and the event brackets stretch whatever runs beside the MFCC):
     # the rocprofv3 timeline of the replayed step under profiles/ is the reference for the in-step figure.
     img_us, img_us_side = {}, {}
-    if not args.no_roofline and HW in (84, 96):
-        tags = (1, 2, 12, 7, 11, 15)
+    if legs and HW in (84, 96):
         for serial, dst in ((True, img_us), (False, img_us_side)):
             old_mask = ctx.set_streams(0) if serial else None
-            for tag in tags:
+            for tag in img_tags:
                 ctx.profile_select(tag)
                 for _ in range(20):
                     eager_step()
@@ -629,6 +659,12 @@ def main():
             ctx.profile_select(-1)
             if serial:
                 ctx.set_streams(old_mask)
+    if not args.full and not args.no_roofline:
+        # a plain run takes the eager steps of the legs above, unprofiled: the timed replays then start at the sustained clock
+        # (see the capture above), and a plain and a --full run time -- and end at -- the same training state
+        for _ in range(3 * len(dom_tags) + 2 * min(args.steps, 100) + 2 * 20 * len(img_tags)):
+            eager_step()
+            torch.cuda.synchronize()
 
     if use_graph:
         tr.sync_device_scalars()                     # (the eager legs above advanced the optimiser's step count)
@@ -701,7 +737,9 @@ def main():
                                 "how": "HIP events around each kernel family over eager steps: alone = every launch on one stream; "
                                        "beside_sound = the step's stream plan (eager: an upper bound of the in-graph durations, see the "
                                        "rocprofv3 timeline under profiles/)"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"loss": tr.loss, "params": model.flat_parameters(), "grads": tr.grads})
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline()
             out["parity_vs_cpu"] = parity_vs_cpu(var_amd, model, pool)
         emit(json.dumps(out))

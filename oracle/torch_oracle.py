@@ -6,7 +6,7 @@ re-declared from torch.nn layers:
     models/pretext/pretext_base.py:10-41       (routing + F.normalize)
     VAR/pretext_VAR.py:33-39,55-70             (Adam, TripletMarginLoss, step body)
 This is what the reference itself executes on a CPU-only host (torch.nn -> oneDNN), so it is the
-`cpu_baseline` that bench.py times beside the HIP path.  Pinned by tests/test_oracle_torch.py
+`cpu_baseline` that bench.py --full times beside the HIP path.  Pinned by tests/test_oracle_torch.py
 against the golden vectors."""
 import torch
 import torch.nn as nn

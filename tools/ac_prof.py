@@ -1,5 +1,5 @@
-import sys, types, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, types, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import var_amd
 class Box:
     def __init__(self, n): self.shape = (n,)

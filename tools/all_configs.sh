@@ -21,9 +21,9 @@ run "" --steps 200 --warmup 20 --no-roofline --no-cpu-baseline
 run "--hw 96" --hw 96 --steps 200 --warmup 20 --no-roofline --no-cpu-baseline
 run "--head inbatch" --head inbatch --steps 200 --warmup 20 --no-roofline --no-cpu-baseline
 run "--rehearse-one-device" --rehearse-one-device --steps 200 --warmup 20 --no-roofline --no-cpu-baseline
-run "--workload ithor" --workload ithor --no-cpu-baseline
+run "--workload ithor" --workload ithor --full --no-cpu-baseline
 cp gpurun_out/_cfg.json gpurun_out/${TAG}_ithor_f32_bench.json
-run "--workload ithor --dtype bf16" --workload ithor --dtype bf16 --no-cpu-baseline
+run "--workload ithor --dtype bf16" --workload ithor --dtype bf16 --full --no-cpu-baseline
 cp gpurun_out/_cfg.json gpurun_out/${TAG}_ithor_bf16_bench.json
 timeout -k 10 300 python tools/infer_latency.py > gpurun_out/${TAG}_config5_latency.txt 2>&1
 cat $OUT gpurun_out/${TAG}_config5_latency.txt

@@ -1,7 +1,8 @@
-import sys, types, numpy as np, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, types, numpy as np, torch
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import var_amd
-fx = dict(np.load('/root/repo/tests/golden/ithor_h96.npz'))
+fx = dict(np.load(os.path.join(ROOT, 'tests', 'golden', 'ithor_h96.npz')))
 cuda = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
 cfg = types.SimpleNamespace(img_dim=(3, 96, 96), sound_dim=(1, 600, 40), representationDim=3)
 res = {}

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Copy the summaries of a tools/checkpoint_profiles.sh run from gpurun_out/ (scratch) into profiles/ (tracked).
-usage: python tools/collect_profiles.py TAG"""
+"""Copy the summaries of a tools/checkpoint_profiles.sh run from its output folder (scratch) into profiles/ (tracked).
+usage: python tools/collect_profiles.py TAG   (the folder: $OUT, default profiling_out/, as for the script)"""
 import glob, os, shutil, subprocess, sys
 tag = sys.argv[1]
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-go, pr = os.path.join(root, "gpurun_out"), os.path.join(root, "profiles")
+go, pr = os.path.join(root, os.environ.get("OUT", "profiling_out")), os.path.join(root, "profiles")
 stats = glob.glob(f"{go}/prof_{tag}/**/*kernel_stats.csv", recursive=True)
 shutil.copy(stats[0], f"{pr}/{tag}_kernel_stats.csv")
 run = lambda *a: subprocess.run([sys.executable] + list(a), capture_output=True, text=True, cwd=root).stdout
