@@ -105,11 +105,12 @@ int var_arm_encoder_fwd(var_ctx* ctx, void* stream, const float* params,
  * Envs/vec_env/vec_pretext_normalize.py:96-101 (`calcReward`: torch.sum(a * b, dim=1)) as ONE launch on `stream`; the sum
  * runs over k in index order in fp32. */
 int var_row_dot(var_ctx* ctx, void* stream, const float* a, const float* b, int rows, int dim, float* out);
-/* Arms the NEXT var_arm_encoder_fwd with an image and at most 32 rows (the RL stage's envs): its image-head launch also leaves
- * reward_out[b] = <image_feat[b], goal_feat[b]> (3 floats per row, var_row_dot's sum) -- the intrinsic reward of
- * VAR/pretext_base.py's calcReward without a launch of its own (each launch is ~5 us on that path).  goal_feat must be complete
- * on the forward's stream (the cached goal embedding of the later steps of an episode).  Disarmed by that forward, or by
- * (NULL, NULL); forwards of more rows ignore it. */
+/* Arms the NEXT var_arm_encoder_fwd with an image: it also leaves reward_out[b] = <image_feat[b], goal_feat[b]> (3 floats per
+ * row, var_row_dot's sum) -- the intrinsic reward of VAR/pretext_base.py's calcReward.  Where the image head is a launch of its
+ * own that finishes the embeddings (save_for_bwd = 2, 84 x 84, at most 16 rows: the RL stage's envs) the dot rides in that launch
+ * (each launch is ~5 us on that path); otherwise the forward adds one row-dot launch after the embeddings.  goal_feat must be
+ * complete on the forward's stream (the cached goal embedding of the later steps of an episode).  Disarmed by that forward,
+ * whatever it ran, or by (NULL, NULL). */
 int var_set_reward_dot(var_ctx* ctx, const float* goal_feat, float* reward_out);
 
 /* autograd backward of the encoder (loss.backward(), VAR/pretext_VAR.py:68) from the
@@ -329,11 +330,11 @@ int var_mfcc_psf(var_ctx* ctx, void* stream, const int16_t* pcm, const int* lens
  * var_profile_select: record HIP events, on the launch stream, around every launch of one
  * kernel family (tag in [0, var_profile_tag_count()), -1 = off); var_profile_read returns the
  * summed durations and the launch count since the select (it synchronises on the events).
- * var_set_streams: which parts of a step leave the caller's stream (bit 0: sound CNN forward, bit 1: sound
- * CNN backward, bit 4: with bit 0, MFCC stays on the caller's stream, bit 5: the one-launch image forward of image-only
- * calls also beside a sound branch -- slower there, kept for timing, bit 6: the training step's forward and backward
- * hand over between their two streams with graph edges again instead of device-side flags, see var_join_status); -1 restores the default (3).
- * 0 puts every kernel on the caller's stream (per-kernel timing).  Returns the old mask.
+ * var_set_streams: which parts of a step leave the caller's stream (bit 0: sound branch forward incl. the in-step MFCC, bit 1:
+ * sound CNN backward, bit 6: the training step's forward and backward hand over between their two streams with graph edges
+ * again instead of device-side flags, see var_join_status; other bits are ignored); -1 restores the default (3).
+ * 0 puts every kernel on the caller's stream (per-kernel timing).  Returns the previous mask, as stored: passing it back
+ * restores it.
  * var_join_status: in a training step recorded under stream capture (var_arm_loss_grad* with all three branches, two
  * streams; launched eagerly the step keeps its stream edges) the backward's first kernels
  * do not wait for the other stream's forward through the streams (a barrier packet in a replayed graph costs ~10 us there):

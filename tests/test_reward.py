@@ -69,6 +69,67 @@ def test_intrinsic_reward_on_hip_encoder(golden_dir):
     assert np.array_equal(dot2.cpu().numpy(), dot1.cpu().numpy())
 
 
+def _kuka_model(golden_dir, hw):
+    """The fixture weights on the GPU at either image size (the image head's 64 x 3 x 3 input is the same at 84 and 96)."""
+    import torch
+    import var_amd
+    sd = dict(np.load(os.path.join(golden_dir, "kuka_weights.npz")))
+    cfg = types.SimpleNamespace(img_dim=(3, hw, hw), sound_dim=(1, 100, 40), representationDim=3)
+    m = var_amd.VARPretextNet(cfg)
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    return m.to("cuda")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hw,B", [(84, 8), (84, 32), (96, 8)])
+def test_image_only_reward_step_is_its_own_dot(golden_dir, hw, B):
+    """The image-only graph of IntrinsicReward returns <image_feat, goal_feat> of ITS OWN step at every size, whether the dot
+    rides in the image-head launch (84 x 84, B <= 16) or is a launch of its own after the embeddings (96 x 96, more rows)."""
+    import torch
+    import var_amd
+    r = var_amd.IntrinsicReward(_kuka_model(golden_dir, hw)).capture(B)
+    rng = np.random.default_rng(hw + B)
+    img1, img2 = (torch.from_numpy(rng.integers(0, 256, size=(B, 3, hw, hw), dtype=np.uint8)).cuda() for _ in range(2))
+    goal = torch.from_numpy(rng.standard_normal((B, 1, 100, 40)).astype(np.float32)).cuda()
+    _, _, dot1 = r.step(img1, goal)
+    dot1 = dot1.cpu().numpy().copy()
+    f2, g2, dot2 = r.step(img2, None)
+    f2, g2, dot2 = f2.cpu().numpy(), g2.cpu().numpy(), dot2.cpu().numpy()
+    want = np.sum(f2 * g2, 1)
+    assert np.max(np.abs(dot2 - want)) < 1e-6, (dot2, want)
+    assert not np.array_equal(dot2, dot1)                  # (different images: not the with-goal step's value)
+
+
+@pytest.mark.gpu
+def test_reward_dot_is_disarmed_by_its_forward(golden_dir):
+    """var_set_reward_dot arms ONE var_arm_encoder_fwd, whichever kernels that forward ran: a later unarmed forward -- here
+    one that takes the in-launch dot path -- writes nothing through the old pointer."""
+    import torch
+    from var_amd._lib import Context, current_stream_handle, ptr
+    c = Context.get(0)
+    B = 8
+    goal = torch.randn(B, 3, device="cuda")
+    X = torch.zeros(B, device="cuda")
+
+    def forward(hw):
+        m = _kuka_model(golden_dir, hw)
+        flat = m.flat_parameters()
+        c.ensure_plan(B, hw)
+        m.hip_weights(c, force=True)
+        img = torch.from_numpy(np.random.default_rng(hw).integers(0, 256, size=(B, 3, hw, hw), dtype=np.uint8)).cuda()
+        feat = torch.empty(B, 3, device="cuda")
+        c.check(c.lib.var_arm_encoder_fwd(c.handle, current_stream_handle(), ptr(flat), ptr(img), 1, img.stride(0), None, None,
+                                          B, hw, ptr(feat), None, None, None, None, 2), "var_arm_encoder_fwd")
+        torch.cuda.synchronize()
+
+    c.check(c.lib.var_set_reward_dot(c.handle, ptr(goal), ptr(X)), "var_set_reward_dot")
+    forward(96)                                            # armed: the dot is a launch of its own at 96 x 96
+    X.fill_(-12345.0)
+    torch.cuda.synchronize()
+    forward(84)                                            # unarmed: 84 x 84, B = 8 would take the in-launch dot
+    assert torch.all(X == -12345.0), X
+
+
 @pytest.mark.gpu
 def test_row_dot_is_calc_reward_and_rejects_bad_arguments():
     """var_row_dot = calcReward's torch.sum(a * b, dim=1) (vec_pretext_normalize.py:96-101) in one launch."""

@@ -32,10 +32,8 @@ int var_init(int device_id, var_ctx** out) {
     if (!c) return VAR_ERR_HIP;
     c->device = device_id;
     // Which parts of a step leave the caller's stream (bit 0: sound branch forward incl. MFCC, bit 1: sound
-    // branch backward, bit 4: with bit 0, the MFCC kernel stays on the caller's stream and only the sound CNN
-    // forks); var_set_streams changes the plan (0 = everything on the caller's stream, for per-kernel timing).
+    // branch backward); var_set_streams changes the mask (0 = everything on the caller's stream, for per-kernel timing).
     c->streams = default_streams();
-    c->serial = c->streams == 0;
     c->pl = make_param_layout();
     c->kl = make_pack_layout();
     if (c->pl.total != VAR_N_PARAMS) {
@@ -295,52 +293,103 @@ __global__ void __launch_bounds__(256) gemb_in_kernel(const float* __restrict__ 
     gemb[2 * n + e] = g2 ? g2[e] : 0.f;
 }
 
-// dev_join: the caller (the fused training step) goes straight on into encoder_bwd, whose first kernel on `s` is the only
-// consumer of the side stream's results: no join here -- that kernel waits for the sound heads on the device (heads.hip)
+__global__ void __launch_bounds__(256) row_dot_kernel(const float* __restrict__ a, const float* __restrict__ b, int rows, int dim,
+                                                      float* __restrict__ out) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    float s = 0.f;
+    for (int k = 0; k < dim; ++k) s += a[(size_t)r * dim + k] * b[(size_t)r * dim + k];
+    out[r] = s;
+}
+
+// inference-only forwards (save_for_bwd = 2) of at most kHead1MaxB images take the round-2 conv 1 + 2 head, at 84 x 84 and at most
+// kSmallMidB images also the small conv 3-5 kernels (img_conv_fwd.hip)
+static constexpr int kHead1MaxB = 64;
+static constexpr int kSmallMidB = 16;
+
+// Which kernels one encoder forward launches and on which streams -- every rule in this one place.  pos / neg: the sound inputs
+// as the forward sees them (the in-step MFCC's output included); finish: the embeddings are to be finished (normalised) by the
+// forward; join_requested / capturing: the caller asked for the device-side hand-over and `s` is being captured; dot_armed:
+// var_set_reward_dot armed this forward.
+static FwdPlan plan_encoder_fwd(int H, int B, int save_for_bwd, bool image, bool pos, bool neg, bool finish, bool join_requested,
+                                bool capturing, int streams, bool dot_armed) {
+    FwdPlan p;
+    const bool fwd_only = save_for_bwd == 2;
+    const bool snd = pos || neg;
+    // The role-specialised head (img_head2.hip) walks an image's seven bands inside ONE workgroup -- the right shape for a full
+    // batch, the wrong one for the RL stage's 8 images, where the per-image latency is the kernel time: an inference-only forward
+    // of a small batch takes the round-2 head, which spreads an image's tiles over workgroups; its NCHW act1 is never read by a
+    // backward.  At 84 x 84 img_head2 leaves act1 band-tiled for img_tail2.hip, at 96 x 96 as NCHW (img_tail2.hip gathers its
+    // bands from the rows).
+    const bool head2 = !(fwd_only && B <= kHead1MaxB);
+    // The one-launch image forward (conv 1-5 + head, img_fwd_all_kernel: one image per workgroup in both halves) takes 71 us
+    // against 41.6 + 36.3 for the two launches -- alone.  Beside the sound branch it LOSES (0.3045 vs 0.3017 ms per step,
+    // alternating runs): the step is bound by CU time, not by the image chain's latency, and the sound kernels get onto the CUs at
+    // the image kernels' boundaries -- one boundary fewer pushes the sound forward behind the whole image forward.  So: image-only
+    // forwards (the frozen encoder at full batch, the projection of a dataset) take the fused launch, a forward with a sound
+    // branch the two launches.
+    if (head2 && H == 84 && B <= kHead2G && !snd) p.img = ImgPath::All;
+    else if (fwd_only && B <= kSmallMidB && H == 84) p.img = ImgPath::Head1Small;
+    else p.img = head2 ? ImgPath::Head2Mid3 : ImgPath::Head1Mid3;
+    p.act1_tiled = head2 && H == 84;
+    p.head_in_conv = p.img != ImgPath::Head1Small;
+    p.conv_finish = p.head_in_conv && finish;
+    // small batches (the RL stage's 8 envs) stay on the caller's stream: every kernel is a few us there and a fork / join pair
+    // costs more than the overlap gives
+    p.fork_ok = (streams & 1) && B > 32;
+    p.mfcc_main = !p.fork_ok;
+    // The device-side hand-over only under stream capture: in a replayed graph both branches sit in the device's queues before
+    // either starts, so a wait can only be as long as the other branch's kernels; launched eagerly, a host thread that is
+    // descheduled between the two branches' launches would turn into a time-out and a step with stale numbers -- and eagerly the
+    // edges' cost drowns in launch overhead.
+    p.dev_join = join_requested && capturing && p.fork_ok && (streams & 2) && !(streams & 64) && image && pos && neg;
+    // The reward's dot rides in the image-head launch where that launch finishes the embeddings itself (one row block: the small
+    // path), and is one row_dot_kernel after the embeddings otherwise
+    if (dot_armed && image && finish) p.dot = p.img == ImgPath::Head1Small ? RewardDot::InHead : RewardDot::RowDot;
+    return p;
+}
+
+// join_requested: the caller (the fused training step) goes straight on into encoder_bwd, whose first kernel on `s` is the only
+// consumer of the side stream's results: no join here when the plan takes the device-side hand-over -- that kernel waits for the
+// sound heads on the device (heads.hip)
 static int encoder_fwd(var_ctx* c, hipStream_t s, const float* params, const void* image, int is_u8,
                        long bstride, const int* image_index, const float* pos, const float* neg,
-                       const AudioIn* audio, int B, bool finish = true, bool dev_join = false) {
+                       const AudioIn* audio, int B, int save_for_bwd, bool finish, bool join_requested, bool dot_armed) {
     int rc;
     if (audio && audio->pcm) {
         pos = c->mfcc_buf;
         neg = c->mfcc_buf + (size_t)B * VAR_MFCC_FRAMES * VAR_MFCC_COEFFS;
     }
     const bool snd = pos || neg;
-    // small batches (the RL stage's 8 envs) stay on the caller's stream: every kernel is a few us there and a
-    // fork / join pair costs more than the overlap gives
-    const bool fork_ok = (c->streams & 1) && B > 32;
-    hipStream_t ss = fork_ok ? c->side : s;
     // (decided before the first launch: the image forward's last kernel raises the flag the sound rows wait for)
-    // Only under stream capture: in a replayed graph both branches sit in the device's queues before either starts, so a wait can
-    // only be as long as the other branch's kernels; launched eagerly, a host thread that is descheduled between the two branches'
-    // launches would turn into a time-out and a step with stale numbers -- and eagerly the edges' cost drowns in launch overhead.
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (dev_join && hipStreamIsCapturing(s, &cap) != hipSuccess) cap = hipStreamCaptureStatusNone;
-    c->dev_join = dev_join && cap == hipStreamCaptureStatusActive && fork_ok && (c->streams & 2) && !(c->streams & 64) && image && pos && neg;
+    if (join_requested && hipStreamIsCapturing(s, &cap) != hipSuccess) cap = hipStreamCaptureStatusNone;
+    const FwdPlan p = plan_encoder_fwd(c->H, B, save_for_bwd, image, pos, neg, finish, join_requested,
+                                       cap == hipStreamCaptureStatusActive, c->streams, dot_armed);
+    c->fwd_plan = p;
+    hipStream_t ss = p.fork_ok ? c->side : s;
     // Launch ORDER matters under graph replay: the chain that is enqueued first after a fork keeps the hardware
     // queue of its predecessor, the other branch pays a cross-queue hand-over (5-10 us).  So the caller's stream
     // (MFCC -> image CNN -> image head) is enqueued first and the sound branch, which has slack, afterwards.
-    const bool mfcc_main = (c->streams & 16) != 0 || !fork_ok;
     bool forked = false;
     if (snd && audio && audio->pcm) {
-        if (!mfcc_main) { if ((rc = fork_side(c, s, 0)) != VAR_OK) return rc; forked = true; }
-        if ((rc = launch_mfcc(c, mfcc_main ? s : ss, audio->pcm, audio->lens, audio->clip_index, 2 * B, audio->pcm_stride,
+        if (!p.mfcc_main) { if ((rc = fork_side(c, s, 0)) != VAR_OK) return rc; forked = true; }
+        if ((rc = launch_mfcc(c, p.mfcc_main ? s : ss, audio->pcm, audio->lens, audio->clip_index, 2 * B, audio->pcm_stride,
                               VAR_MFCC_FRAMES, c->mfcc_buf)) != VAR_OK) return rc;
     }
-    if (snd && fork_ok && !forked && (rc = fork_side(c, s, 0)) != VAR_OK) return rc;     // the side stream starts after the caller's prior work
-    // The one-launch image forward (conv 1-5 + head, img_fwd_all_kernel) takes 71 us against 41.6 + 36.3 for the two launches --
-    // alone.  Beside the sound branch it LOSES (0.3045 vs 0.3017 ms per step, alternating runs): the step is bound by CU time, not
-    // by the image chain's latency, and the sound kernels get onto the CUs at the image kernels' boundaries -- one boundary fewer
-    // pushes the sound forward behind the whole image forward.  So: image-only forwards (the frozen encoder at full batch, the
-    // projection of a dataset) take the fused launch, a forward with a sound branch the two launches.
-    c->fuse_fwd = c->fuse_fwd_always || !snd;
-    c->mid_finish = finish;
-    if (image && (rc = launch_img_fwd(c, s, params, image, is_u8, bstride, image_index, B)) != VAR_OK) return rc;
-    if (image && (rc = launch_heads_fwd(c, s, s, params, B, true, false, false, finish)) != VAR_OK) return rc;
+    if (snd && p.fork_ok && !forked && (rc = fork_side(c, s, 0)) != VAR_OK) return rc;     // the side stream starts after the caller's prior work
+    if (image) {
+        if ((rc = launch_img_fwd(c, s, p, params, image, is_u8, bstride, image_index, B)) != VAR_OK) return rc;
+        if ((rc = launch_heads_fwd(c, s, s, p, params, B, true, false, false, finish)) != VAR_OK) return rc;
+        if (p.dot == RewardDot::RowDot) {
+            hipLaunchKernelGGL(row_dot_kernel, dim3((B + 255) / 256), dim3(256), 0, s, (const float*)c->emb, c->dot_with, B, kEmb, c->dot_out);
+            VAR_HIP_CHECK(c, hipGetLastError());
+        }
+    }
     if (snd) {
         if ((rc = launch_snd_fwd(c, ss, params, pos, neg, B)) != VAR_OK) return rc;
-        if ((rc = launch_heads_fwd(c, ss, ss, params, B, false, pos != nullptr, neg != nullptr, finish)) != VAR_OK) return rc;
-        if (fork_ok && !c->dev_join && (rc = join_side(c, s, 0)) != VAR_OK) return rc;
+        if ((rc = launch_heads_fwd(c, ss, ss, p, params, B, false, pos != nullptr, neg != nullptr, finish)) != VAR_OK) return rc;
+        if (p.fork_ok && !p.dev_join && (rc = join_side(c, s, 0)) != VAR_OK) return rc;
     }
     c->saved_B = B;
     c->saved_gen = ++c->fwd_gen;
@@ -365,12 +414,12 @@ int var_arm_encoder_fwd(var_ctx* c, void* stream, const float* params, const voi
     if ((rc = check_weights(c, params, "var_arm_encoder_fwd")) != VAR_OK) return rc;
     SET_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
-    c->fwd_only = save_for_bwd == 2;                // inference with the small-batch kernels (img_conv_fwd.hip)
     // the normalised embeddings go to the caller's buffers from the heads' finish kernels themselves
     c->out_img = image ? image_feat : nullptr; c->out_pos = mfcc_pos ? pos_feat : nullptr; c->out_neg = mfcc_neg ? neg_feat : nullptr;
-    rc = encoder_fwd(c, s, params, image, image_is_u8, image_bstride, nullptr, mfcc_pos, mfcc_neg, nullptr, B);
-    c->fwd_only = false;
+    rc = encoder_fwd(c, s, params, image, image_is_u8, image_bstride, nullptr, mfcc_pos, mfcc_neg, nullptr, B, save_for_bwd, true,
+                     false, c->dot_out != nullptr);
     c->out_img = c->out_pos = c->out_neg = nullptr;
+    c->dot_with = nullptr; c->dot_out = nullptr;      // (var_set_reward_dot arms one forward)
     if (rc != VAR_OK) return rc;
     if (save_for_bwd != 1) c->saved_B = 0;
     CopySegs S{};
@@ -383,15 +432,6 @@ int var_arm_encoder_fwd(var_ctx* c, void* stream, const float* params, const voi
         VAR_HIP_CHECK(c, hipGetLastError());
     }
     return VAR_OK;
-}
-
-__global__ void __launch_bounds__(256) row_dot_kernel(const float* __restrict__ a, const float* __restrict__ b, int rows, int dim,
-                                                      float* __restrict__ out) {
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= rows) return;
-    float s = 0.f;
-    for (int k = 0; k < dim; ++k) s += a[(size_t)r * dim + k] * b[(size_t)r * dim + k];
-    out[r] = s;
 }
 
 int var_row_dot(var_ctx* c, void* stream, const float* a, const float* b, int rows, int dim, float* out) {
@@ -427,12 +467,13 @@ static int encoder_bwd(var_ctx* c, hipStream_t s, const float* params, float* gr
     // (same ordering rule as in the forward: the caller's chain first, then the side branch)
     // (dev_join: the side stream has not been joined since the forward's fork and needs no edge from `s` either: its rows kernel
     // waits for the image partials on the device)
-    if (!c->dev_join && (rc = fork_side(c, s, 1)) != VAR_OK) return rc;
+    const bool dev_join = c->fwd_plan.dev_join;
+    if (!dev_join && (rc = fork_side(c, s, 1)) != VAR_OK) return rc;
     if (c->saved_image) {
-        if ((rc = launch_heads_bwd(c, s, s, params, grads, B, true, 0, 0, fused, margin, inv_count, fused ? loss_out : nullptr)) != VAR_OK) return rc;
+        if ((rc = launch_heads_bwd(c, s, s, params, grads, B, true, 0, 0, dev_join, fused, margin, inv_count, fused ? loss_out : nullptr)) != VAR_OK) return rc;
         if ((rc = launch_img_bwd(c, s, params, grads, B)) != VAR_OK) return rc;
     }
-    if ((rc = launch_heads_bwd(c, ss, ss, params, grads, B, false, snd_lo, snd_hi, fused, margin, inv_count)) != VAR_OK) return rc;
+    if ((rc = launch_heads_bwd(c, ss, ss, params, grads, B, false, snd_lo, snd_hi, dev_join, fused, margin, inv_count)) != VAR_OK) return rc;
     // (fused: the loss value is summed by the image head's backward from the terms its rows kernel leaves -- heads.hip)
     if ((rc = launch_snd_bwd(c, ss, params, grads, B)) != VAR_OK) return rc;
     return join_side(c, s, 1);
@@ -475,11 +516,11 @@ static int loss_grad_impl(var_ctx* c, hipStream_t s, const float* params, const 
     // and no triplet kernel on the caller's chain.  (With feats_out the separate finish / triplet kernels run:
     // tests/test_gpu_round2.py::test_config2_batch256_full_batch_parity covers both.)
     const bool fused = !feats_out && image && (mfcc_pos || (audio && audio->pcm)) && (mfcc_neg || (audio && audio->pcm));
-    if ((rc = encoder_fwd(c, s, params, image, image_is_u8, image_bstride, image_index, mfcc_pos, mfcc_neg, audio, B,
-                          !fused, fused)) != VAR_OK) return rc;
+    if ((rc = encoder_fwd(c, s, params, image, image_is_u8, image_bstride, image_index, mfcc_pos, mfcc_neg, audio, B, 1,
+                          !fused, fused, false)) != VAR_OK) return rc;
     if (fused) {
         rc = encoder_bwd(c, s, params, grads, true, margin, inv_count, loss_out);
-        c->dev_join = false;
+        c->fwd_plan.dev_join = false;            // (the hand-over is this backward's: a later var_arm_encoder_bwd takes the edges)
         return rc;
     }
     if ((rc = launch_triplet(c, s, c->emb, c->emb + 3 * B, c->emb + 6 * B, B, margin, inv_count, loss_out,
@@ -617,9 +658,7 @@ static int default_streams() { return kDefaultStreams; }
 int var_set_streams(var_ctx* c, int mask) {
     if (!c) return -1;
     const int old = c->streams;
-    c->streams = mask < 0 ? default_streams() : (mask & (19 | 64));   // bit 6: keep the graph edge between the forward's two streams
-    c->serial = c->streams == 0;
-    c->fuse_fwd_always = mask >= 0 && (mask & 32);   // bit 5: the one-launch image forward even beside a sound branch (A/B timing, tests)
+    c->streams = mask < 0 ? default_streams() : (mask & (3 | 64));   // bit 6: keep the graph edge between the forward's two streams
     return old;
 }
 
@@ -681,7 +720,7 @@ int var_debug_buffer(var_ctx* c, const char* name, void** ptr, long* nfloats) {
         const long n = (long)(B * kImgCh[l] * c->hs[l] * c->hs[l]);
         if (!strcmp(name, a)) {
             *ptr = c->act[l]; *nfloats = n;
-            if (l == 1 && c->H == 84 && c->act1_tiled) {          // the tiled form -> NCHW, into the (otherwise unused) gact[1] block
+            if (l == 1 && c->fwd_plan.act1_tiled) {          // the tiled form -> NCHW, into the (otherwise unused) gact[1] block
                 int rc = launch_act1_untile(c, nullptr, (int)B);
                 if (rc != VAR_OK) return rc;
                 VAR_HIP_CHECK(c, hipStreamSynchronize(nullptr));

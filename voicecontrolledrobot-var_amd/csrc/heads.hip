@@ -679,8 +679,8 @@ heads_finish_kernel(const float* __restrict__ part, const float* __restrict__ b1
 template <int K>
 static int run_heads_fwd(var_ctx* c, hipStream_t s, const float* x, int R, const float* w0t, const float* b0,
                          const float* w1, const float* b1, float* hid, float* emb_raw, float* emb, float* part,
-                         bool finish, float* out0 = nullptr, float* out1 = nullptr, int split = 0, unsigned* sig = nullptr,
-                         unsigned* sig_other = nullptr) {
+                         bool finish, float* out0, float* out1, int split, unsigned* sig, unsigned* sig_other,
+                         const float* dot_with = nullptr, float* dot_out = nullptr) {
     constexpr int A1 = 32 * (K + 1) * 4, A2 = 5 * 32 * 33 * 4;
     constexpr int LDS_BYTES = A1 > A2 ? A1 : A2;
     static unsigned attr_set = 0;      // bit d: set on device d (function attributes are per device)
@@ -689,32 +689,29 @@ static int run_heads_fwd(var_ctx* c, hipStream_t s, const float* x, int R, const
                                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
         attr_set |= var_dev_bit(c);
     }
-    // one row block and a finish wanted: the last workgroup finishes (FinishArgs above); the reward's row dot rides along when
-    // var_set_reward_dot armed it for this (image) head
+    // one row block and a finish wanted: the last workgroup finishes (FinishArgs above), and takes the reward's row dot when the
+    // plan put it here (plan_encoder_fwd: RewardDot::InHead)
     const bool fin_in = finish && R <= 32 && !sig;
-    FinishArgs fin{b1, emb_raw, emb, out0, out1, split, fin_in ? c->jsig + 12 : nullptr, nullptr, nullptr};
-    if (fin_in && K == kImgFeat && c->dot_out) { fin.dot_with = c->dot_with; fin.dot_out = c->dot_out; }
-    if (K == kImgFeat) { c->dot_with = nullptr; c->dot_out = nullptr; }          // (armed for one forward)
+    FinishArgs fin{b1, emb_raw, emb, out0, out1, split, fin_in ? c->jsig + 12 : nullptr, dot_with, dot_out};
     hipLaunchKernelGGL(heads_fwd_split_kernel<K>, dim3((R + 31) / 32, 4), dim3(256), LDS_BYTES, s, x, R, w0t, b0, w1, hid, part, sig, sig_other, fin);
     if (finish && !fin_in) hipLaunchKernelGGL(heads_finish_kernel, dim3((R + 255) / 256), dim3(256), 0, s, part, b1, R, emb_raw, emb, out0, out1, split);
     return VAR_OK;
 }
 
-int launch_heads_fwd(var_ctx* c, hipStream_t s, hipStream_t ss, const float* params, int B, bool has_img,
+// the heads that the image forward did not run (plan_encoder_fwd): with p.head_in_conv the conv 3-5 kernel already left hid_i,
+// the 128 -> 3 partials of every image and, with p.conv_finish, the image embeddings themselves
+int launch_heads_fwd(var_ctx* c, hipStream_t s, hipStream_t ss, const FwdPlan& p, const float* params, int B, bool has_img,
                      bool has_pos, bool has_neg, bool finish) {
     const ParamLayout& L = c->pl;
     const PackLayout& K = c->kl;
     int rc;
-    if (has_img && c->head_in_mid) {
-        // the fused conv 3-5 kernel already left hid_i and the 128 -> 3 partials of every image -- and, when a finish was wanted
-        // (var_ctx::mid_finish), the embeddings themselves
-        if (finish && !c->mid_finish) hipLaunchKernelGGL(heads_finish_kernel, dim3((B + 255) / 256), dim3(256), 0, s, c->head_part,
-                                                         params + L.ih_b1, B, c->emb_raw, c->emb, c->out_img, (float*)nullptr, B);
-    } else if (has_img) {
+    if (has_img && !p.head_in_conv) {
         ProfScope prof(c, s, TAG_HEADS_FWD);
+        const bool dot = p.dot == RewardDot::InHead;
         if ((rc = run_heads_fwd<kImgFeat>(c, s, c->act[5], B, c->wpack + K.ih_w0t, params + L.ih_b0, params + L.ih_w1,
                                           params + L.ih_b1, c->hid_i, c->emb_raw, c->emb, c->head_part, finish, c->out_img, nullptr, B,
-                                          c->dev_join ? c->jsig + 4 : nullptr, c->jsig)) != VAR_OK) return rc;
+                                          p.dev_join ? c->jsig + 4 : nullptr, c->jsig, dot ? c->dot_with : nullptr,
+                                          dot ? c->dot_out : nullptr)) != VAR_OK) return rc;
     }
     if (has_pos || has_neg) {
         const int lo = has_pos ? 0 : B, hi = has_neg ? 2 * B : B;
@@ -723,7 +720,7 @@ int launch_heads_fwd(var_ctx* c, hipStream_t s, hipStream_t ss, const float* par
                                           c->hid_s + (size_t)lo * kHid, c->emb_raw + 3 * (B + lo),
                                           c->emb + 3 * (B + lo), c->head_part + 16 * (size_t)(B + lo), finish,
                                           lo == 0 ? c->out_pos : nullptr, c->out_neg, lo == 0 ? B : 0,
-                                          c->dev_join ? c->jsig : nullptr, c->jsig + 4)) != VAR_OK) return rc;
+                                          p.dev_join ? c->jsig : nullptr, c->jsig + 4)) != VAR_OK) return rc;
     }
     VAR_HIP_CHECK(c, hipGetLastError());
     return VAR_OK;
@@ -750,7 +747,7 @@ int launch_triplet_loss(var_ctx* c, hipStream_t s, const float* params, int B, f
 // gemb (3B,3) must hold the gradients wrt the normalised embeddings [img | pos | neg].
 // Produces gact[5] (B,576), gsact[4] (2B,160) and the 8 head gradient tensors.
 int launch_heads_bwd(var_ctx* c, hipStream_t s, hipStream_t ss, const float* params, float* grads, int B, bool has_img,
-                     int snd_lo, int snd_hi, bool fused, float margin, float inv_count, float* loss_out) {
+                     int snd_lo, int snd_hi, bool dev_join, bool fused, float margin, float inv_count, float* loss_out) {
     const ParamLayout& L = c->pl;
     const size_t mB = (size_t)c->maxB;
     float* graw = c->gemb + 9 * mB;                       // (3B,4)
@@ -787,7 +784,7 @@ int launch_heads_bwd(var_ctx* c, hipStream_t s, hipStream_t ss, const float* par
             if (fused)
                 hipLaunchKernelGGL(heads_bwd_rows_fused_kernel, dim3(B), dim3(128), 0, s, B, B, 0, params + L.ih_w1,
                                    c->hid_i, c->head_part, params + L.ih_b1, params + L.sh_b1, margin, inv_count,
-                                   c->emb_raw, c->emb, graw, c->ghid, ghidT, c->dev_join ? c->jsig : nullptr, 6, lterms);
+                                   c->emb_raw, c->emb, graw, c->ghid, ghidT, dev_join ? c->jsig : nullptr, 6, lterms);
             else
                 hipLaunchKernelGGL(heads_bwd_rows_kernel, dim3(B), dim3(128), 0, s, B, params + L.ih_w1, c->hid_i,
                                    c->emb_raw, c->emb, c->gemb, graw, c->ghid, ghidT);
@@ -798,7 +795,7 @@ int launch_heads_bwd(var_ctx* c, hipStream_t s, hipStream_t ss, const float* par
                 hipLaunchKernelGGL(heads_bwd_rows_fused_kernel, dim3(R), dim3(128), 0, ss, R, B, B + snd_lo,
                                    params + L.sh_w1, c->hid_s + (size_t)snd_lo * kHid, c->head_part, params + L.ih_b1,
                                    params + L.sh_b1, margin, inv_count, c->emb_raw, c->emb, graw + 4 * (B + snd_lo),
-                                   c->ghid + (size_t)(B + snd_lo) * kHid, ghidT + (size_t)B * kHid, c->dev_join ? c->jsig + 4 : nullptr, 1,
+                                   c->ghid + (size_t)(B + snd_lo) * kHid, ghidT + (size_t)B * kHid, dev_join ? c->jsig + 4 : nullptr, 1,
                                    (float*)nullptr);
             else
                 hipLaunchKernelGGL(heads_bwd_rows_kernel, dim3(R), dim3(128), 0, ss, R, params + L.sh_w1,

@@ -618,7 +618,7 @@ img_fwd_all_kernel(const void* __restrict__ image, long bstride, const int* __re
 // conv 1 .. conv 5 + image head at 84 x 84 as ONE launch (one image per workgroup: B <= 256); leaves act[1] (band-tiled), act[2..5],
 // hid_i and the head partials like launch_img_fwd_head2 + launch_img_fwd_mid
 int launch_img_fwd_all(var_ctx* c, hipStream_t s, const float* params, const void* image, int is_u8, long bstride,
-                       const int* image_index, int B) {
+                       const int* image_index, int B, unsigned* sig, const float* fin_b1) {
     using CM = M3Cfg<21>;
     ProfScope prof(c, s, TAG_IMG_FWD0 + 1);
     const ParamLayout& L = c->pl;
@@ -634,8 +634,8 @@ int launch_img_fwd_all(var_ctx* c, hipStream_t s, const float* params, const voi
         hipLaunchKernelGGL(kern, dim3(B), dim3(M3_NT), CM::LDS_BYTES, s, image, bstride, image_index, c->wpack + K.img_f[0],
                            c->wpack + K.img_f[1], c->act[1], c->act[2], c->wpack + K.img_f[2], c->wpack + K.img_f[3], c->wpack + K.img_f[4],
                            params, L.img_b[0], L.img_b[1], L.img_b[2], L.img_b[3], L.img_b[4], L.ih_b0, L.ih_w1, c->act[3], c->act[4],
-                           c->act[5], c->wpack + K.ih_w0t, c->hid_i, c->head_part, B, c->dev_join ? c->jsig + 4 : nullptr,
-                           MidFinish{c->mid_finish ? params + L.ih_b1 : nullptr, c->emb_raw, c->emb, c->out_img});
+                           c->act[5], c->wpack + K.ih_w0t, c->hid_i, c->head_part, B, sig,
+                           MidFinish{fin_b1, c->emb_raw, c->emb, c->out_img});
         VAR_HIP_CHECK(c, hipGetLastError());
         return VAR_OK;
     };
@@ -643,9 +643,9 @@ int launch_img_fwd_all(var_ctx* c, hipStream_t s, const float* params, const voi
 }
 
 // conv 3 + conv 4 + conv 5 of the image CNN (act2 21 x 21 for 84 x 84 inputs, 24 x 24 for 96 x 96); leaves act[3], act[4],
-// act[5] and, with_head, the image head's hidden layer (hid_i) and 128 -> 3 partials (head_part rows [0, B))
+// act[5], the image head's hidden layer (hid_i) and 128 -> 3 partials (head_part rows [0, B)) and, with fin_b1, the image embeddings
 template <int H2>
-static int launch_mid3(var_ctx* c, hipStream_t s, const float* params, int B, bool with_head) {
+static int launch_mid3(var_ctx* c, hipStream_t s, const float* params, int B, unsigned* sig, const float* fin_b1) {
     using C = M3Cfg<H2>;
     static unsigned attr = 0;      // bit d: set on device d (function attributes are per device)
     if (!(attr & var_dev_bit(c))) {
@@ -656,14 +656,13 @@ static int launch_mid3(var_ctx* c, hipStream_t s, const float* params, int B, bo
     const PackLayout& K = c->kl;
     hipLaunchKernelGGL((img_mid3_kernel<C>), dim3(B), dim3(M3_NT), C::LDS_BYTES, s, c->act[2], c->wpack + K.img_f[2],
                        c->wpack + K.img_f[3], c->wpack + K.img_f[4], params, L.img_b[2], L.img_b[3], L.img_b[4], L.ih_b0, L.ih_w1,
-                       c->act[3], c->act[4], c->act[5], with_head ? c->wpack + K.ih_w0t : nullptr, c->hid_i, c->head_part,
-                       (with_head && c->dev_join) ? c->jsig + 4 : nullptr,
-                       MidFinish{(with_head && c->mid_finish) ? params + L.ih_b1 : nullptr, c->emb_raw, c->emb, c->out_img});
+                       c->act[3], c->act[4], c->act[5], c->wpack + K.ih_w0t, c->hid_i, c->head_part, sig,
+                       MidFinish{fin_b1, c->emb_raw, c->emb, c->out_img});
     VAR_HIP_CHECK(c, hipGetLastError());
     return VAR_OK;
 }
 
-int launch_img_fwd_mid(var_ctx* c, hipStream_t s, const float* params, int B, bool with_head) {
+int launch_img_fwd_mid(var_ctx* c, hipStream_t s, const float* params, int B, unsigned* sig, const float* fin_b1) {
     ProfScope prof(c, s, TAG_IMG_FWD0 + 2);
-    return c->H == 84 ? launch_mid3<21>(c, s, params, B, with_head) : launch_mid3<24>(c, s, params, B, with_head);
+    return c->H == 84 ? launch_mid3<21>(c, s, params, B, sig, fin_b1) : launch_mid3<24>(c, s, params, B, sig, fin_b1);
 }

@@ -631,6 +631,10 @@ int launch_tail2(var_ctx* c, hipStream_t s, int B) {
 // weight gradient of conv 2 + data gradient of conv 2 + weight gradient of conv 1 at 84 x 84: consumes gact[2], act[1] and the
 // saved input image; leaves layer 0's and layer 1's slabs (c->wg_groups[0..1] of them) for launch_img_wgrad_reduce
 int launch_img_bwd_tail2(var_ctx* c, hipStream_t s, int B) {
+    if (c->fwd_plan.act1_tiled != (c->H == 84)) {       // band-tiled act1 at 84 x 84, NCHW at 96 x 96 (plan_encoder_fwd)
+        VAR_SET_ERR(c, "image backward: the saved forward left act1 in the other layout");
+        return VAR_ERR_STATE;
+    }
     if (c->H == 96) return c->saved_u8 ? launch_tail2<Tail2Cfg<true, 48, 4, false>>(c, s, B) : launch_tail2<Tail2Cfg<false, 48, 4, false>>(c, s, B);
     return c->saved_u8 ? launch_tail2<Tail2Cfg<true, 42, 6, true>>(c, s, B) : launch_tail2<Tail2Cfg<false, 42, 6, true>>(c, s, B);
 }

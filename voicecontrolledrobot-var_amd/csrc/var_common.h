@@ -107,6 +107,30 @@ struct var_weights {
     var_ctx* owner = nullptr;
 };
 
+// Which kernels one Kuka encoder forward launches: decided once, before its first launch, by plan_encoder_fwd (api.hip), and
+// handed to the launchers.
+enum class ImgPath {
+    All,          // img_fwd_all_kernel: conv 1-5 + image head in one launch (img_mid3.hip)
+    Head2Mid3,    // img_head2 (conv 1 + 2) + img_mid3 (conv 3-5 + image head)
+    Head1Mid3,    // the round-2 img_fwd_head (conv 1 + 2) + img_mid3 (conv 3-5 + image head)
+    Head1Small,   // img_fwd_head + three c3f::launch_small (conv 3, 4, 5) + the image head as its own launch (heads.hip)
+};
+enum class RewardDot {
+    None,         // no dot armed (var_set_reward_dot), or nothing to take it from
+    InHead,       // the image-head launch finishes the embeddings and takes the dot in the same launch (heads.hip)
+    RowDot,       // one row_dot_kernel over the image rows of emb, after the embeddings are final
+};
+struct FwdPlan {
+    ImgPath img = ImgPath::Head2Mid3;
+    bool act1_tiled = false;      // act1 leaves band-tiled (img_head2.hip, 84 x 84) rather than NCHW
+    bool head_in_conv = false;    // the image head runs inside the conv kernel (img_mid3.hip) ...
+    bool conv_finish = false;     // ... which also finishes the image embeddings
+    bool fork_ok = false;         // the sound branch runs on the side stream
+    bool mfcc_main = true;        // the in-step MFCC runs on the caller's stream
+    bool dev_join = false;        // the forward leaves the side stream un-joined: the backward's rows wait on jsig (heads.hip)
+    RewardDot dot = RewardDot::None;
+};
+
 struct var_ctx {
     int device = 0;
     char err[512] = {0};
@@ -142,9 +166,9 @@ struct var_ctx {
     // heads' forward workgroups, [1] completed launches of that kernel, [2] how many of them the caller's stream has waited for,
     // [3] waits for it that timed out (sticky; var_join_status); [4..7] the same for the conv 3-5 kernel and the side stream
     unsigned* jsig = nullptr;
-    const float* dot_with = nullptr;   // var_set_reward_dot: the next small-batch image-head forward also leaves <emb, dot_with> rows in dot_out
+    const float* dot_with = nullptr;   // var_set_reward_dot: the next var_arm_encoder_fwd also leaves <emb, dot_with> rows in dot_out
     float* dot_out = nullptr;
-    bool dev_join = false;        // this step's forward left the side stream un-joined: the image rows wait on jsig[1]
+    FwdPlan fwd_plan;             // what the last encoder forward launched (plan_encoder_fwd): its backward and var_debug_buffer read it
     float* slabs = nullptr;       // split-K partial weight gradients
     size_t slab_floats = 0;
     size_t snd_slab_off = 0;
@@ -158,11 +182,6 @@ struct var_ctx {
     // saved forward
     // var_arm_encoder_fwd's embedding outputs: the finish kernels of the heads write them directly (no copy launch afterwards)
     float *out_img = nullptr, *out_pos = nullptr, *out_neg = nullptr;
-    bool head_in_mid = false;             // the last image forward also ran the image head (img_mid3.hip)
-    bool mid_finish = false;              // ... and is to finish the image embeddings too (encoder_fwd: finish wanted)
-    bool fuse_fwd_always = false;         // var_set_streams bit 5
-    bool fuse_fwd = false;                // 84 x 84, B <= 256: conv 1-5 + image head as ONE launch (img_fwd_all_kernel).  Set per call by
-                                          // encoder_fwd (api.hip): image-only forwards, or always with var_set_streams bit 5 -- see there
     int saved_B = 0;
     const void* saved_image = nullptr;
     int saved_u8 = 0;
@@ -171,10 +190,7 @@ struct var_ctx {
     const float* saved_neg = nullptr;
     const int* saved_index = nullptr;     // optional image gather index of the saved forward
     // side stream for the sound branch (runs beside the image branch) and its fork/join events
-    bool act1_tiled = false;              // the last image forward left act1 band-tiled (img_head2.hip) rather than NCHW
-    bool fwd_only = false;                // the running forward saves nothing for a backward (var_arm_encoder_fwd, save_for_bwd = 0)
-    bool serial = false;                  // var_set_streams(0): everything on the caller's stream (per-kernel profiling)
-    int streams = 0;              // bit mask, see var_init
+    int streams = 0;              // bit mask, see var_set_streams
     hipStream_t side = nullptr;
     hipEvent_t ev_fork[2] = {nullptr, nullptr}, ev_join[2] = {nullptr, nullptr};
     float* mfcc_buf = nullptr;            // (2*maxB, 100, 40) when the front-end runs inside the step
@@ -300,7 +316,7 @@ size_t snd_slab_floats();
 
 // kernels' host launchers (one per .hip file) ------------------------------------------
 int launch_pack_weights(var_ctx* c, hipStream_t s, const float* params);
-int launch_img_fwd(var_ctx* c, hipStream_t s, const float* params, const void* image, int is_u8,
+int launch_img_fwd(var_ctx* c, hipStream_t s, const FwdPlan& p, const float* params, const void* image, int is_u8,
                    long bstride, const int* image_index, int B);
 int launch_img_fwd_head(var_ctx* c, hipStream_t s, const float* params, const void* image, int is_u8, long bstride,
                         const int* image_index, int B);
@@ -317,12 +333,15 @@ int launch_img_fwd_head2(var_ctx* c, hipStream_t s, const float* params, const v
 #define VAR_HEAD2_G 256
 #endif
 static constexpr int kHead2G = VAR_HEAD2_G;   // persistent workgroups of img_head2_kernel (one image = NB tiles each)
-int launch_img_fwd_mid(var_ctx* c, hipStream_t s, const float* params, int B, bool with_head);
+// img_mid3.hip: sig = the device-side hand-over flag the image head raises (nullptr: none), fin_b1 = the image head's output bias
+// when the kernel also finishes the image embeddings (nullptr: it leaves the partials only)
+int launch_img_fwd_mid(var_ctx* c, hipStream_t s, const float* params, int B, unsigned* sig, const float* fin_b1);
 int launch_img_fwd_all(var_ctx* c, hipStream_t s, const float* params, const void* image, int is_u8, long bstride,
-                       const int* image_index, int B);      // img_mid3.hip: conv 1-5 + image head in one launch (84 x 84, B <= 256)
+                       const int* image_index, int B, unsigned* sig,
+                       const float* fin_b1);      // conv 1-5 + image head in one launch (84 x 84, B <= 256)
 // default: the whole sound branch -- MFCC front-end, sound CNN and sound head, forward and backward -- beside the image
-// CNN on one side stream.  (Round 1 kept the 61-us MFCC on the caller's stream, mask 19; with round 2's 43-us kernel the
-// image chain starting at once and the front-end on the side stream is 4-5 us per step faster: 0.346 vs 0.351 ms.)  Measured on MI355X (graph replay):
+// CNN on one side stream.  (Round 1 kept the 61-us MFCC on the caller's stream; with round 2's 43-us kernel the image chain
+// starting at once and the front-end on the side stream is 4-5 us per step faster: 0.346 vs 0.351 ms.)  Measured on MI355X (graph replay):
 // every cross-stream edge costs several us, and two GPU-filling persistent kernels side by side slow each other
 // down more than the overlap gains -- only the small sound kernels are worth forking.
 static constexpr int kDefaultStreams = 3;
@@ -335,10 +354,11 @@ int launch_img_bwd_tail2(var_ctx* c, hipStream_t s, int B);   // img_tail2.hip: 
 int launch_img_bwd(var_ctx* c, hipStream_t s, const float* params, float* grads, int B);
 int launch_snd_fwd(var_ctx* c, hipStream_t s, const float* params, const float* pos, const float* neg, int B);
 int launch_snd_bwd(var_ctx* c, hipStream_t s, const float* params, float* grads, int B);
-int launch_heads_fwd(var_ctx* c, hipStream_t s, hipStream_t ss, const float* params, int B, bool has_img, bool has_pos,
-                     bool has_neg, bool finish = true);
+int launch_heads_fwd(var_ctx* c, hipStream_t s, hipStream_t ss, const FwdPlan& p, const float* params, int B, bool has_img,
+                     bool has_pos, bool has_neg, bool finish);
 int launch_heads_bwd(var_ctx* c, hipStream_t s, hipStream_t ss, const float* params, float* grads, int B, bool has_img,
-                     int snd_lo, int snd_hi, bool fused = false, float margin = 0.f, float inv_count = 0.f, float* loss_out = nullptr);
+                     int snd_lo, int snd_hi, bool dev_join, bool fused = false, float margin = 0.f, float inv_count = 0.f,
+                     float* loss_out = nullptr);
 int launch_triplet_loss(var_ctx* c, hipStream_t s, const float* params, int B, float margin, float inv_count,
                         float* loss_out);
 int launch_triplet(var_ctx* c, hipStream_t s, const float* a, const float* p, const float* n, int B,
