@@ -317,6 +317,29 @@ int var_armnet_forward(var_ctx* ctx, void* stream, const float* params, const vo
 int var_armnet_status(var_ctx* ctx, unsigned* word);
 int var_armnet_clear_status(var_ctx* ctx);
 
+/* iTHOR RL actor-critic forward -------------------------------------------------------------------------------
+ * Policy.act up to the sampling (models/ppo/model.py:57-69) for base 'ai2thor_VAR' (Envs/ai2thor/config.py:71):
+ * ai2thorNet_VAR.forward (models/RL/ai2thor_RL_model.py:87-121: the 96x96 image stack, the 9x9 occupancy branch, recurrent:
+ * one GRU(128 -> 1024) step from rnn_hxs * masks) and the linear layer of Categorical (n_actions logits).  params =
+ * Policy.state_dict() back to back in registration order (base.gru.*, base.imgCNN.{0,2,5,8,11,14},
+ * base.occupancyCNNMLP.{0,2,5,7}, base.motorMlp, cnnMlp, imgMotorMlp, imgMotorMlp2, soundMlp, fusionMlp, mlp_all, actor,
+ * critic, critic_linear, dist.linear): var_ithor_policy_param_count(n_actions) floats (5 475 081 at 8 actions; 1 <= n_actions
+ * <= 16, else VAR_ERR_ARG).
+ *   image (B,3,96,96) and occupancy (B,1,9,9, contiguous), each u8 (divided by 255) or f32 already divided; image_feat (B,3),
+ *   goal_sound_feat (B,3), rnn_hxs (B,1024), masks (B,1)  ->  value (B,1), actor_features (B,128), logits (B,n_actions, may be
+ *   NULL), rnn_hxs_out (B,1024).  Sampling / log-probabilities stay with the caller.
+ * Kernel paths as var_armnet_forward's (same results within 2e-5): B <= 64 images on the LDS-band convolutions, B <= 8 rows
+ * on the one-launch MLP chain, which reports time-outs through var_ithor_policy_status / var_ithor_policy_clear_status with
+ * var_armnet_status's semantics.  rnn_hxs_out must not overlap rnn_hxs (VAR_ERR_ARG). */
+int var_ithor_policy_param_count(int n_actions);
+int var_ithor_policy_plan(var_ctx* ctx, int max_batch);
+int var_ithor_policy_forward(var_ctx* ctx, void* stream, const float* params, int n_actions, const void* image, int image_is_u8,
+                             long image_bstride, const void* occupancy, int occupancy_is_u8, const float* image_feat,
+                             const float* goal_sound_feat, const float* rnn_hxs, const float* masks, int B,
+                             float* value, float* actor_features, float* logits, float* rnn_hxs_out);
+int var_ithor_policy_status(var_ctx* ctx, unsigned* word);
+int var_ithor_policy_clear_status(var_ctx* ctx);
+
 /* The iTHOR/FSC audio front-end: python_speech_features.mfcc as called at Envs/audioLoader.py:158-161 (pre-emphasis
  * .97, 400/160 frames with a zero-padded tail, np.hamming, |rfft_512|^2/512, 40 triangles, log, orthonormal DCT-II,
  * lifter 22, coefficient 0 = log frame energy; int16 samples NOT normalised) + processSoundFeat (:241-252).

@@ -41,7 +41,7 @@ def show(d, n_avg=40):
     f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)[0]
     rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))
     names = [r["Kernel_Name"] for r in rows]
-    ends = [i for i, n in enumerate(names) if "armnet_chain" in n]          # the chain kernel closes a forward
+    ends = [i for i, n in enumerate(names) if "mlp_chain" in n]          # the chain kernel closes a forward
     steps = [rows[a + 1:b + 1] for a, b in zip(ends[:-1], ends[1:])][-n_avg:]
     steps = [st for st in steps if len(st) == len(steps[-1])]
     k = len(steps[-1])

@@ -69,6 +69,11 @@ _SIGNATURES = {
     "var_set_reward_dot": (_i, [_vp, _vp, _vp]),
     "var_armnet_clear_status": (_i, [_vp]),
     "var_debug_armnet_drop_workgroup": (_i, [_vp]),
+    "var_ithor_policy_param_count": (_i, [_i]),
+    "var_ithor_policy_plan": (_i, [_vp, _i]),
+    "var_ithor_policy_forward": (_i, [_vp, _vp, _vp, _i, _vp, _i, _l, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "var_ithor_policy_status": (_i, [_vp, _vp]),
+    "var_ithor_policy_clear_status": (_i, [_vp]),
     "var_mfcc_psf": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "var_ithor_param_count": (_i, []),
     "var_ithor_plan": (_i, [_vp, _i, _i]),

@@ -1,0 +1,495 @@
+// iTHOR RL actor-critic forward on gfx950: models/RL/ai2thor_RL_model.py:7-121 `ai2thorNet_VAR` (96x96 image stack: 6
+// convolutions / 4 max pools -> 1152, the occupancy branch: 2 convolutions 9 -> 5 -> 3 + 2 Linear layers, the motor / image /
+// sound MLPs, one GRU(128 -> 1024) step through NNBase._forward_gru's acting path, models/ppo/model.py:116-121, fusion and the
+// actor / critic trunks) followed by Categorical's logit layer (models/ppo/distributions.py), i.e. everything of Policy.act
+// up to the sampling.  Inference only.  The same three regimes as armnet.hip: up to 64 images the image stack runs on the
+// LDS-band kernels of c3f.h (filters re-packed per call inside conv 1's launch), up to 8 rows the 22 Linear layers + GRU
+// step run as one persistent launch (chain.h), larger batches take the gather-GEMM of gg.h layer by layer with the
+// parameters in place in their state_dict() layouts.
+#include <string.h>
+
+#include "gg.h"
+
+namespace {
+PH_DECL();
+}
+#include "c3f.h"
+#include "chain.h"
+
+namespace {
+constexpr int kCh[7] = {3, 32, 32, 64, 64, 128, 128};       // imgCNN channels, conv l: kCh[l - 1] -> kCh[l]
+constexpr int kSide[7] = {96, 96, 96, 48, 24, 12, 3};       // output side of conv l (before its pool)
+constexpr int kRepr = 3, kRin = 128, kRh = 1024, kAct = 128, kFlat = 1152, kOcc = 288, kMaxActions = 16;
+
+struct Lin { int w, b, in, out; };
+struct PolLayout {
+    int g_wih, g_whh, g_bih, g_bhh;
+    int cw[6], cb[6];          // imgCNN.{0,2,5,8,11,14}
+    int ow[2], ob[2];          // occupancyCNNMLP.{0,2}
+    Lin occ[2];                // occupancyCNNMLP.{5,7}
+    Lin motor[2], cnn[2], im[2], im2, snd[3], fus[2], all[2], actor[2], critic[2], clin, logit;
+    int total;
+};
+
+PolLayout make_layout(int n_actions) {
+    PolLayout L{};
+    int o = 0;
+    L.g_wih = o; o += 3 * kRh * kRin; L.g_whh = o; o += 3 * kRh * kRh; L.g_bih = o; o += 3 * kRh; L.g_bhh = o; o += 3 * kRh;
+    for (int i = 0; i < 6; i++) { L.cw[i] = o; o += kCh[i + 1] * kCh[i] * 9; L.cb[i] = o; o += kCh[i + 1]; }
+    L.ow[0] = o; o += 64 * 9; L.ob[0] = o; o += 64;
+    L.ow[1] = o; o += 32 * 64 * 9; L.ob[1] = o; o += 32;
+    auto lin = [&](int in, int out) { Lin l{o, o + in * out, in, out}; o += in * out + out; return l; };
+    L.occ[0] = lin(kOcc, 128); L.occ[1] = lin(128, 256);
+    L.motor[0] = lin(kRepr, 64); L.motor[1] = lin(64, 256);
+    L.cnn[0] = lin(kFlat, 512); L.cnn[1] = lin(512, 256);
+    L.im[0] = lin(256, 64); L.im[1] = lin(64, kRin);
+    L.im2 = lin(kRh, 256);
+    L.snd[0] = lin(kRepr, 128); L.snd[1] = lin(128, 256); L.snd[2] = lin(256, 256);
+    L.fus[0] = lin(256, 512); L.fus[1] = lin(512, 256);
+    L.all[0] = lin(256, 256); L.all[1] = lin(256, 128);
+    L.actor[0] = lin(128, 128); L.actor[1] = lin(128, kAct);
+    L.critic[0] = lin(128, 128); L.critic[1] = lin(128, 128);
+    L.clin = lin(128, 1);
+    L.logit = lin(kAct, n_actions);
+    L.total = o;
+    return L;
+}
+
+// the image stack as band kernels (c3f.h), bands / channel groups chosen for 192-256 workgroups at 8 images
+using IpC2 = c3f::Cfg<32, 32, 96, 4, 2, 1, true>;        // 96 -> pool 48: 192 workgroups
+using IpC3 = c3f::Cfg<32, 64, 48, 6, 1, 1, true>;        // 48 -> pool 24: 256
+using IpC4 = c3f::Cfg<64, 64, 24, 4, 1, 1, true>;        // 24 -> pool 12: 192
+using IpC5 = c3f::Cfg<64, 128, 12, 4, 1, 1, true>;       // 12 -> pool 6: 192
+using IpC6 = c3f::SmallCfg<128, 128, 6, 2, 3, 1>;        // stride 2 pad 1, 6 -> 3: 64
+constexpr int kBandMaxB = 64;      // beyond this the gather-GEMM's big tiles win
+constexpr long kSlab = 8L << 20;   // floats of split-K scratch
+constexpr long kChainFloats = (long)kChainRows * 32768;
+
+struct pol_state {
+    int n_actions = 0;
+    PolLayout L;
+    int maxB = 0;
+    float* ws = nullptr;
+    float *a[7] = {nullptr}, *p[5] = {nullptr};        // conv outputs 1..6 (a[2..5]: the gather-GEMM path only), pooled maps 1..4
+    float* occf = nullptr;                             // (B, 288): the occupancy convolutions' flattened output
+    float *t0 = nullptr, *t1 = nullptr, *t2 = nullptr, *t3 = nullptr;     // (B, 512) scratch rows
+    float *flat_img = nullptr, *motor = nullptr, *occ = nullptr, *sound = nullptr, *fusion = nullptr, *h0 = nullptr;
+    float *h1 = nullptr, *gi = nullptr, *gh = nullptr, *slab = nullptr;   // h1: the new hidden state (B, 1024)
+    float* chain = nullptr;
+    unsigned* sync = nullptr;          // chain.h: [1] finished workgroups, [2] epoch of the last timed-out launch, [3] next epoch, [4] sticky
+    c3f::f32x4* wpk = nullptr;         // conv 2..6 filters in MFMA A-fragment order, re-packed per forward
+    c3f::PackDesc pack{};
+};
+
+// occupancyCNNMLP's two convolutions (1 -> 64, 3x3 s2 p1, 9 -> 5; 64 -> 32, 3x3 s2 p1, 5 -> 3; ReLU each): 0.2 MFLOP per env,
+// the (B, 288) flattened maps feed the first occupancy Linear layer.  A workgroup = (env, kOccCo output channels of the second
+// convolution): it recomputes the first one (14 K FMAs), stages its share of the second filter in LDS and splits each output's
+// 576 products over kOccKs threads (one thread per output streaming them from memory took 100 us, from LDS 32 us).
+constexpr int kOccT = 256, kOccCo = 2, kOccKs = 8;
+template <bool U8>
+__global__ void __launch_bounds__(kOccT) ip_occ_kernel(const void* __restrict__ occ, const float* __restrict__ P, int w0, int b0, int w1,
+                                                      int b1, float* __restrict__ out) {
+    __shared__ float x[81];
+    __shared__ float h[64 * 25];
+    __shared__ float wl[kOccCo * 64 * 9];
+    const int b = blockIdx.x / (32 / kOccCo), co0 = (blockIdx.x % (32 / kOccCo)) * kOccCo, tid = threadIdx.x;
+    if (tid < 81) x[tid] = U8 ? (float)((const uint8_t*)occ)[(long)b * 81 + tid] / 255.f : ((const float*)occ)[(long)b * 81 + tid];
+    for (int e = tid; e < kOccCo * 64 * 9; e += kOccT) wl[e] = P[w1 + (long)co0 * 64 * 9 + e];
+    __syncthreads();
+    for (int e = tid; e < 64 * 25; e += kOccT) {
+        const int co = e / 25, py = (e % 25) / 5, px = e % 5;
+        float s = 0.f;
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const int iy = 2 * py - 1 + ky, ix = 2 * px - 1 + kx;
+                if (iy >= 0 && iy < 9 && ix >= 0 && ix < 9) s = fmaf(P[w0 + co * 9 + ky * 3 + kx], x[iy * 9 + ix], s);
+            }
+        s += P[b0 + co];
+        h[e] = s > 0.f ? s : 0.f;
+    }
+    __syncthreads();
+    // second convolution: kOccCo * 9 outputs x kOccKs slices of 64 / kOccKs input channels, the partial sums folded in slice order
+    constexpr int NO = kOccCo * 9, CS = 64 / kOccKs;
+    __shared__ float red[kOccKs * NO];
+    if (tid < NO * kOccKs) {
+        const int o = tid % NO, sl = tid / NO, col = o / 9, py = (o % 9) / 3, px = o % 3;
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < CS; ++c) {
+            const int ci = sl * CS + c;
+#pragma unroll
+            for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+                for (int kx = 0; kx < 3; ++kx) {
+                    const int iy = 2 * py - 1 + ky, ix = 2 * px - 1 + kx;
+                    if (iy >= 0 && iy < 5 && ix >= 0 && ix < 5) s = fmaf(wl[(col * 64 + ci) * 9 + ky * 3 + kx], h[ci * 25 + iy * 5 + ix], s);
+                }
+        }
+        red[sl * NO + o] = s;
+    }
+    __syncthreads();
+    if (tid < NO) {
+        float s = red[tid];
+#pragma unroll
+        for (int sl = 1; sl < kOccKs; ++sl) s += red[sl * NO + tid];
+        s += P[b1 + co0 + tid / 9];
+        out[(long)b * kOcc + co0 * 9 + tid] = s > 0.f ? s : 0.f;
+    }
+}
+
+static __global__ void ip_pool_kernel(const float* __restrict__ x, float* __restrict__ y, long n, int H, int HP) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int px = (int)(i % HP), py = (int)((i / HP) % HP);
+    const long plane = i / ((long)HP * HP);
+    const float* q = x + plane * H * H + (long)(2 * py) * H + 2 * px;
+    y[i] = fmaxf(fmaxf(q[0], q[1]), fmaxf(q[H], q[H + 1]));
+}
+static __global__ void ip_add_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = a[i] + b[i];
+}
+static __global__ void ip_mask_kernel(const float* __restrict__ h, const float* __restrict__ mask, float* __restrict__ out, int B, int H) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < B * H) out[i] = h[i] * mask[i / H];
+}
+// torch.nn.GRU cell (gate order r, z, n); gi / gh include their biases
+static __global__ void ip_gru_cell_kernel(const float* __restrict__ gi, const float* __restrict__ gh, const float* __restrict__ h,
+                                          float* __restrict__ out, float* __restrict__ out2, int B, int H) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * H) return;
+    const int b = i / H, j = i - b * H;
+    const float* a = gi + (long)b * 3 * H;
+    const float* g = gh + (long)b * 3 * H;
+    const float r = 1.f / (1.f + expf(-(a[j] + g[j])));
+    const float z = 1.f / (1.f + expf(-(a[H + j] + g[H + j])));
+    const float n = tanhf(a[2 * H + j] + r * g[2 * H + j]);
+    const float v = (1.f - z) * n + z * h[i];
+    out[i] = v;
+    out2[i] = v;
+}
+
+inline dim3 g1(long n) { return dim3((unsigned)((n + 255) / 256)); }
+#define IP_CHECK(c) VAR_HIP_CHECK(c, hipGetLastError())
+#define RUN(x) do { int r_ = (x); if (r_ != VAR_OK) return r_; } while (0)
+
+template <class G, bool U8>
+int conv(var_ctx* c, hipStream_t s, pol_state* st, const ConvDims& d, const void* x, const float* w, const float* bias, float* y) {
+    ConvFwdP<G, U8, false> p{};
+    p.M = d.B * d.HO * d.WO; p.N = d.COUT; p.K = d.CIN * G::KHW;
+    const long out = (long)p.M * p.N;
+    p.nsplit = gg_small_split(((p.M + GG_MT - 1) / GG_MT) * ((p.N + 63) / 64), p.K, out, kSlab);
+    p.d = d; p.x = x; p.w = w; p.bias = bias; p.y = y; p.slab = st->slab; p.sstride = out;
+    RUN(gg_launch(c, s, p));
+    if (p.nsplit > 1) {
+        hipLaunchKernelGGL(gg_finish_kernel, g1(out), dim3(256), 0, s, y, st->slab, out, p.nsplit, out, bias, d.COUT, d.HO * d.WO, 1);
+        IP_CHECK(c);
+    }
+    return VAR_OK;
+}
+int linear(var_ctx* c, hipStream_t s, pol_state* st, const float* P, const Lin& l, const float* X, float* Y, int rows, int relu) {
+    const long out = (long)rows * l.out;
+    const int ns = gg_small_split(((l.out + GG_MT - 1) / GG_MT) * ((rows + 63) / 64), l.in, out, kSlab);
+    if (ns > 1) {
+        DenseP<true, true, 2> p{};
+        p.M = l.out; p.N = rows; p.K = l.in; p.nsplit = ns;
+        p.A = P + l.w; p.sam = l.in; p.sak = 1; p.Bm = X; p.sbk = 1; p.sbn = l.in; p.C = st->slab; p.scm = 1; p.scn = l.out; p.sC = out;
+        RUN(gg_launch(c, s, p));
+        hipLaunchKernelGGL(gg_finish_kernel, g1(out), dim3(256), 0, s, Y, st->slab, out, ns, out, P + l.b, l.out, 1, relu);
+        IP_CHECK(c);
+        return VAR_OK;
+    }
+    DenseP<true, true, 0> p{};
+    p.M = l.out; p.N = rows; p.K = l.in; p.nsplit = 1;
+    p.A = P + l.w; p.sam = l.in; p.sak = 1; p.Bm = X; p.sbk = 1; p.sbn = l.in; p.C = Y; p.scm = 1; p.scn = l.out;
+    p.bias = P + l.b; p.relu = relu;
+    return gg_launch(c, s, p);
+}
+int add(var_ctx* c, hipStream_t s, const float* a, const float* b, float* out, int n) {
+    hipLaunchKernelGGL(ip_add_kernel, g1(n), dim3(256), 0, s, a, b, out, n);
+    IP_CHECK(c);
+    return VAR_OK;
+}
+
+// Everything after the convolutions for B <= 8 rows as ONE persistent launch (chain.h).  Stages (jobs of one stage run side
+// by side; W_hh . (h * mask) depends on kernel inputs only and streams its 12.6 MB in the first stage):
+//   1 cnnMlp.0 (1152 -> 512), motorMlp.0 (3 -> 64), soundMlp.0 (3 -> 128), occupancy Linear 0 (288 -> 128), W_hh (1024 -> 3072)
+//   2 cnnMlp.2 -> image_flatten, motorMlp.2 -> motor, soundMlp.2, occupancy Linear 1 -> occupancy
+//   3 imgMotorMlp.0 (image_flatten + motor + occupancy), soundMlp.4 -> sound
+//   4 imgMotorMlp.2, fusionMlp.0 (sound + image_flatten)      5 W_ih (128 -> 3072), fusionMlp.2 -> fusion
+//   6 GRU cell -> imgMotorMlp2      7 mlp_all.0 (fusion + imageMotorRnn)      8 mlp_all.2
+//   9 critic.0, actor.0      10 critic.2, actor.2 -> actor features      11 critic_linear -> value, Categorical linear -> logits
+int chain_forward(var_ctx* c, hipStream_t s, pol_state* st, const float* P, const float* image_feat, const float* goal,
+                  const float* hxs, const float* masks, int B, float* value, float* actor_features, float* logits, float* hxs_out) {
+    const PolLayout& L = st->L;
+    ChainDesc D{};
+    D.P = P; D.B = B; D.H = kRh; D.sync = st->sync;
+    enum { A6, OCCF, IMGF, GOAL, HXS, MASK, HOUT, VALUE, AFEAT, LOGITS, CNN0, FLAT, M0, MOTOR, S0, S1, SOUND, O0, OCC, GH, IM0, X, F0,
+           FUSION, GI, IMR, ALL0, ALL1, C0, C1, A0, AFT, NBUF };
+    static_assert(NBUF <= kChainBufs, "buffer table");
+    float* sc = st->chain;
+    auto scratch = [&](int width) { float* p = sc; sc += kChainRows * width * 2; return p; };     // (value, tag) pairs
+    D.buf[A6] = st->a[6]; D.buf[OCCF] = st->occf; D.buf[IMGF] = (float*)image_feat; D.buf[GOAL] = (float*)goal;
+    D.buf[HXS] = (float*)hxs; D.buf[MASK] = (float*)masks; D.buf[HOUT] = hxs_out; D.buf[VALUE] = value; D.buf[AFEAT] = actor_features;
+    D.buf[LOGITS] = logits ? logits : scratch(kMaxActions);
+    const int widths[][2] = {{CNN0, 512}, {FLAT, 256}, {M0, 64}, {MOTOR, 256}, {S0, 128}, {S1, 256}, {SOUND, 256}, {O0, 128},
+                             {OCC, 256}, {GH, 3 * kRh}, {IM0, 64}, {X, kRin}, {F0, 512}, {FUSION, 256}, {GI, 3 * kRh}, {IMR, 256},
+                             {ALL0, 256}, {ALL1, 128}, {C0, 128}, {C1, 128}, {A0, 128}, {AFT, kAct}};
+    for (auto& wd : widths) { D.buf[wd[0]] = scratch(wd[1]); D.tagged |= 1ull << wd[0]; }      // handed over inside the launch
+    D.b_hxs = HXS; D.b_mask = MASK; D.b_hout = HOUT;
+    ChainBuilder cb(D);
+    auto job = [&](const Lin& l, int kind, int in0, int in1, int out, int relu, int out2 = -1, int in2 = -1) {
+        cb.job(l.w, l.b, l.in, l.out, kind, in0, in1, 0, out, relu, out2, in2);
+    };
+    const Lin ih{L.g_wih, L.g_bih, kRin, 3 * kRh}, hh{L.g_whh, L.g_bhh, kRh, 3 * kRh};
+    cb.stage(); job(L.cnn[0], IN_PLAIN, A6, -1, CNN0, 1); job(L.motor[0], IN_PLAIN, IMGF, -1, M0, 1); job(L.snd[0], IN_PLAIN, GOAL, -1, S0, 1);
+                job(L.occ[0], IN_PLAIN, OCCF, -1, O0, 1); job(hh, IN_MASK, HXS, MASK, GH, 0);
+    cb.split();
+    cb.stage(); job(L.cnn[1], IN_PLAIN, CNN0, -1, FLAT, 1); job(L.motor[1], IN_PLAIN, M0, -1, MOTOR, 1); job(L.snd[1], IN_PLAIN, S0, -1, S1, 1);
+                job(L.occ[1], IN_PLAIN, O0, -1, OCC, 1);
+    cb.split();
+    cb.stage(); job(L.im[0], IN_SUM, FLAT, MOTOR, IM0, 1, -1, OCC); job(L.snd[2], IN_PLAIN, S1, -1, SOUND, 1);
+    cb.split();
+    cb.stage(); job(L.im[1], IN_PLAIN, IM0, -1, X, 1); job(L.fus[0], IN_SUM, SOUND, FLAT, F0, 1);
+    cb.split();
+    cb.stage(); job(ih, IN_PLAIN, X, -1, GI, 0); job(L.fus[1], IN_PLAIN, F0, -1, FUSION, 1);
+    cb.split();
+    cb.stage(); job(L.im2, IN_GRU, GI, GH, IMR, 1);                                  // the GRU cell is its input transform
+    cb.split();
+    cb.stage(); job(L.all[0], IN_SUM, FUSION, IMR, ALL0, 1);
+    cb.split();
+    cb.stage(); job(L.all[1], IN_PLAIN, ALL0, -1, ALL1, 1);
+    cb.split();
+    cb.stage(); job(L.critic[0], IN_PLAIN, ALL1, -1, C0, 1); job(L.actor[0], IN_PLAIN, ALL1, -1, A0, 1);
+    cb.split();
+    cb.stage(); job(L.critic[1], IN_PLAIN, C0, -1, C1, 1); job(L.actor[1], IN_PLAIN, A0, -1, AFT, 1, AFEAT);
+    cb.split();
+    cb.stage(); job(L.clin, IN_PLAIN, C1, -1, VALUE, 0); job(L.logit, IN_PLAIN, AFT, -1, LOGITS, 0);
+    cb.split();
+    D.nstages = cb.ns;
+    if (cb.overflow() || sc - st->chain > kChainFloats) {
+        VAR_SET_ERR(c, "ithor policy chain: table overflow");
+        return VAR_ERR_ARG;
+    }
+    return chain_launch(c, s, D, cb.lds_max, kChainG);
+}
+
+// B > 8 rows: one launch per Linear layer (+ the sums, the mask and the GRU cell)
+int layer_forward(var_ctx* c, hipStream_t s, pol_state* st, const float* P, const float* image_feat, const float* goal,
+                  const float* hxs, const float* masks, int B, float* value, float* actor_features, float* logits, float* hxs_out) {
+    const PolLayout& L = st->L;
+    // image_flatten = cnnMlp(flatten), motor = motorMlp(image_feat), occupancy = the occupancy Linear layers
+    RUN(linear(c, s, st, P, L.cnn[0], st->a[6], st->t0, B, 1));
+    RUN(linear(c, s, st, P, L.cnn[1], st->t0, st->flat_img, B, 1));
+    RUN(linear(c, s, st, P, L.motor[0], image_feat, st->t0, B, 1));
+    RUN(linear(c, s, st, P, L.motor[1], st->t0, st->motor, B, 1));
+    RUN(linear(c, s, st, P, L.occ[0], st->occf, st->t0, B, 1));
+    RUN(linear(c, s, st, P, L.occ[1], st->t0, st->occ, B, 1));
+    // imageMotor = imgMotorMlp(image_flatten + motor + occupancy)
+    RUN(add(c, s, st->flat_img, st->motor, st->t0, B * 256));
+    RUN(add(c, s, st->t0, st->occ, st->t1, B * 256));
+    RUN(linear(c, s, st, P, L.im[0], st->t1, st->t0, B, 1));
+    RUN(linear(c, s, st, P, L.im[1], st->t0, st->t2, B, 1));                       // (B,128)
+    // one GRU step from hxs * masks (models/ppo/model.py:118-121)
+    hipLaunchKernelGGL(ip_mask_kernel, g1((long)B * kRh), dim3(256), 0, s, hxs, masks, st->h0, B, kRh);
+    IP_CHECK(c);
+    {
+        const Lin ih{L.g_wih, L.g_bih, kRin, 3 * kRh}, hh{L.g_whh, L.g_bhh, kRh, 3 * kRh};
+        RUN(linear(c, s, st, P, ih, st->t2, st->gi, B, 0));
+        RUN(linear(c, s, st, P, hh, st->h0, st->gh, B, 0));
+        hipLaunchKernelGGL(ip_gru_cell_kernel, g1((long)B * kRh), dim3(256), 0, s, st->gi, st->gh, st->h0, st->h1, hxs_out, B, kRh);
+        IP_CHECK(c);
+    }
+    RUN(linear(c, s, st, P, L.im2, st->h1, st->t0, B, 1));                         // imageMotorRnn (B,256)
+    // sound, fusion
+    RUN(linear(c, s, st, P, L.snd[0], goal, st->t1, B, 1));
+    RUN(linear(c, s, st, P, L.snd[1], st->t1, st->t2, B, 1));
+    RUN(linear(c, s, st, P, L.snd[2], st->t2, st->sound, B, 1));
+    RUN(add(c, s, st->sound, st->flat_img, st->t1, B * 256));
+    RUN(linear(c, s, st, P, L.fus[0], st->t1, st->t2, B, 1));
+    RUN(linear(c, s, st, P, L.fus[1], st->t2, st->fusion, B, 1));
+    RUN(add(c, s, st->fusion, st->t0, st->t1, B * 256));
+    RUN(linear(c, s, st, P, L.all[0], st->t1, st->t2, B, 1));
+    RUN(linear(c, s, st, P, L.all[1], st->t2, st->t3, B, 1));                      // x (B,128)
+    RUN(linear(c, s, st, P, L.critic[0], st->t3, st->t0, B, 1));
+    RUN(linear(c, s, st, P, L.critic[1], st->t0, st->t1, B, 1));
+    RUN(linear(c, s, st, P, L.clin, st->t1, value, B, 0));
+    RUN(linear(c, s, st, P, L.actor[0], st->t3, st->t0, B, 1));
+    RUN(linear(c, s, st, P, L.actor[1], st->t0, actor_features, B, 1));
+    if (logits) RUN(linear(c, s, st, P, L.logit, actor_features, logits, B, 0));
+    return VAR_OK;
+}
+}  // namespace
+
+void ithor_policy_free(var_ctx* c) {
+    pol_state* st = (pol_state*)c->ipol;
+    if (!st) return;
+    if (st->ws) (void)hipFree(st->ws);
+    delete st;
+    c->ipol = nullptr;
+}
+
+extern "C" {
+
+int var_ithor_policy_param_count(int n_actions) {
+    if (n_actions < 1 || n_actions > kMaxActions) return VAR_ERR_ARG;
+    return make_layout(n_actions).total;
+}
+
+int var_ithor_policy_plan(var_ctx* c, int max_batch) {
+    if (!c) return VAR_ERR_ARG;
+    if (max_batch < 1 || max_batch > 4096) { VAR_SET_ERR(c, "var_ithor_policy_plan: batch %d outside 1..4096", max_batch); return VAR_ERR_ARG; }
+    VAR_HIP_CHECK(c, hipSetDevice(c->device));
+    pol_state* st = (pol_state*)c->ipol;
+    if (st && st->maxB >= max_batch) return VAR_OK;
+    if (st) {      // retire (do not free) the superseded workspace: a captured act() graph may still replay on it
+        if (st->ws) { int rc = retire_block(c, st->ws); if (rc != VAR_OK) return rc; }
+        delete st;
+        c->ipol = nullptr;
+    }
+    st = new pol_state();
+    c->ipol = st;
+    st->maxB = max_batch;
+    const long B = max_batch;
+    long total = 0;
+    auto take = [&](long n) { long o = total; total += (n + 63) & ~63L; return o; };
+    long oa[7], op[5];
+    for (int l = 1; l <= 6; ++l) oa[l] = take(B * kCh[l] * kSide[l] * kSide[l]);
+    op[1] = take(B * 32 * 48 * 48); op[2] = take(B * 64 * 24 * 24); op[3] = take(B * 64 * 12 * 12); op[4] = take(B * 128 * 6 * 6);
+    const long oocf = take(B * kOcc);
+    const long ot0 = take(B * 512), ot1 = take(B * 512), ot2 = take(B * 512), ot3 = take(B * 512);
+    const long ofl = take(B * 256), omo = take(B * 256), ooc = take(B * 256), osn = take(B * 256), ofu = take(B * 256), oh0 = take(B * kRh), oh1 = take(B * kRh);
+    const long ogi = take(B * 3 * kRh), ogh = take(B * 3 * kRh), oslab = take(kSlab);
+    const long ochain = take(kChainFloats), osync = take(64);
+    {
+        const PolLayout L = make_layout(1);           // (the convolutions sit before the action-sized layer)
+        c3f::PackDesc& d = st->pack;
+        d.n_layers = 5;
+        int f4 = 0;
+        for (int i = 0; i < 5; ++i) {
+            const int l = i + 1;                      // imgCNN conv l+1: kCh[l] -> kCh[l + 1]
+            d.w_off[i] = L.cw[l]; d.cin[i] = kCh[l]; d.cout[i] = kCh[l + 1];
+            d.wp_off[i] = f4; d.first[i] = f4;
+            f4 += kCh[l] * kCh[l + 1] * 9 / 4;
+        }
+        d.first[5] = f4;
+    }
+    const long owpk = take(4L * st->pack.first[5]);
+    VAR_HIP_CHECK(c, hipMalloc((void**)&st->ws, (size_t)total * sizeof(float)));
+    float* w = st->ws;
+    for (int l = 1; l <= 6; ++l) st->a[l] = w + oa[l];
+    for (int l = 1; l <= 4; ++l) st->p[l] = w + op[l];
+    st->occf = w + oocf;
+    st->t0 = w + ot0; st->t1 = w + ot1; st->t2 = w + ot2; st->t3 = w + ot3;
+    st->flat_img = w + ofl; st->motor = w + omo; st->occ = w + ooc; st->sound = w + osn; st->fusion = w + ofu; st->h0 = w + oh0; st->h1 = w + oh1;
+    st->gi = w + ogi; st->gh = w + ogh; st->slab = w + oslab;
+    st->chain = w + ochain; st->sync = (unsigned*)(w + osync);
+    st->wpk = (c3f::f32x4*)(w + owpk);
+    VAR_HIP_CHECK(c, hipMemset(st->chain, 0, (size_t)kChainFloats * sizeof(float)));       // no tag of any launch yet
+    {
+        const unsigned init[4] = {0u, 0u, 0u, 1u};                  // [3]: the first launch's epoch
+        VAR_HIP_CHECK(c, hipMemset(st->sync, 0, 64 * sizeof(float)));
+        VAR_HIP_CHECK(c, hipMemcpy(st->sync, init, sizeof(init), hipMemcpyHostToDevice));
+    }
+    return VAR_OK;
+}
+
+int var_ithor_policy_forward(var_ctx* c, void* stream, const float* params, int n_actions, const void* image, int image_is_u8,
+                             long image_bstride, const void* occupancy, int occupancy_is_u8, const float* image_feat,
+                             const float* goal_sound_feat, const float* rnn_hxs, const float* masks, int B, float* value,
+                             float* actor_features, float* logits, float* rnn_hxs_out) {
+    if (!c) return VAR_ERR_ARG;
+    VAR_HIP_CHECK(c, hipSetDevice(c->device));
+    pol_state* st = (pol_state*)c->ipol;
+    if (!st || B > st->maxB) { VAR_SET_ERR(c, "var_ithor_policy_forward: var_ithor_policy_plan(%d) first", B); return VAR_ERR_PLAN; }
+    if (!params || !image || !occupancy || !image_feat || !goal_sound_feat || !rnn_hxs || !masks || !value || !actor_features ||
+        !rnn_hxs_out || B < 1) {
+        VAR_SET_ERR(c, "var_ithor_policy_forward: NULL argument or B < 1");
+        return VAR_ERR_ARG;
+    }
+    if (n_actions < 1 || n_actions > kMaxActions) {
+        VAR_SET_ERR(c, "var_ithor_policy_forward: n_actions %d outside 1..%d", n_actions, kMaxActions);
+        return VAR_ERR_ARG;
+    }
+    if (image_bstride < 3L * 96 * 96) {
+        VAR_SET_ERR(c, "var_ithor_policy_forward: image stride %ld < 3*96*96", image_bstride);
+        return VAR_ERR_ARG;
+    }
+    {   // the small-batch chain reads rnn_hxs from every workgroup of its GRU stage while one of them writes rnn_hxs_out
+        const char *a0 = (const char*)rnn_hxs, *b0 = (const char*)rnn_hxs_out;
+        const size_t n = (size_t)B * kRh * sizeof(float);
+        if (a0 < b0 + n && b0 < a0 + n) {
+            VAR_SET_ERR(c, "var_ithor_policy_forward: rnn_hxs_out overlaps rnn_hxs (an in-place state update is not supported)");
+            return VAR_ERR_ARG;
+        }
+    }
+    if (st->n_actions != n_actions) { st->L = make_layout(n_actions); st->n_actions = n_actions; }
+    hipStream_t s = (hipStream_t)stream;
+    const PolLayout& L = st->L;
+    const float* P = params;
+    // occupancyCNNMLP's convolutions (any batch)
+    if (occupancy_is_u8) hipLaunchKernelGGL(ip_occ_kernel<true>, dim3(B * (32 / kOccCo)), dim3(kOccT), 0, s, occupancy, P, L.ow[0], L.ob[0], L.ow[1], L.ob[1], st->occf);
+    else hipLaunchKernelGGL(ip_occ_kernel<false>, dim3(B * (32 / kOccCo)), dim3(kOccT), 0, s, occupancy, P, L.ow[0], L.ob[0], L.ow[1], L.ob[1], st->occf);
+    IP_CHECK(c);
+    // imgCNN
+    if (B <= kBandMaxB) {
+        const c3f::PackDesc& d = st->pack;
+        const int nconv = B * c3f::C1_BANDS, npack = (d.first[5] + 255) / 256;      // conv 1 and the filter pack of conv 2..6: one launch
+        if (image_is_u8) hipLaunchKernelGGL(c3f::c1f_pack_kernel<true>, dim3(nconv + npack), dim3(256), 0, s, image, image_bstride, P, L.cw[0],
+                                            L.cb[0], st->a[1], nconv, st->wpk, d);
+        else hipLaunchKernelGGL(c3f::c1f_pack_kernel<false>, dim3(nconv + npack), dim3(256), 0, s, image, image_bstride, P, L.cw[0], L.cb[0],
+                                st->a[1], nconv, st->wpk, d);
+        IP_CHECK(c);
+        RUN(c3f::launch<IpC2>(c, s, st->a[1], st->wpk + d.wp_off[0], P + L.cb[1], st->p[1], B));
+        RUN(c3f::launch<IpC3>(c, s, st->p[1], st->wpk + d.wp_off[1], P + L.cb[2], st->p[2], B));
+        RUN(c3f::launch<IpC4>(c, s, st->p[2], st->wpk + d.wp_off[2], P + L.cb[3], st->p[3], B));
+        RUN(c3f::launch<IpC5>(c, s, st->p[3], st->wpk + d.wp_off[3], P + L.cb[4], st->p[4], B));
+        RUN(c3f::launch_small<IpC6>(c, s, st->p[4], st->wpk + d.wp_off[4], P + L.cb[5], st->a[6], B));
+    } else {
+        using S1 = Geo<3, 3, 1, 1, 1, 1>;
+        using S2P1 = Geo<3, 3, 2, 2, 1, 1>;
+        auto dims = [&](int l, int hin, int stride) { return conv_dims(B, kCh[l - 1], hin, hin, kCh[l], 3, 3, stride, stride, 1, 1); };
+        auto pool = [&](const float* x, float* y, int ch, int hin) -> int {
+            const long n = (long)B * ch * (hin / 2) * (hin / 2);
+            hipLaunchKernelGGL(ip_pool_kernel, g1(n), dim3(256), 0, s, x, y, n, hin, hin / 2);
+            IP_CHECK(c);
+            return VAR_OK;
+        };
+        ConvDims d1 = dims(1, 96, 1);
+        d1.xb = image_bstride;
+        if (image_is_u8) RUN((conv<S1, true>(c, s, st, d1, image, P + L.cw[0], P + L.cb[0], st->a[1])));
+        else RUN((conv<S1, false>(c, s, st, d1, image, P + L.cw[0], P + L.cb[0], st->a[1])));
+        RUN((conv<S1, false>(c, s, st, dims(2, 96, 1), st->a[1], P + L.cw[1], P + L.cb[1], st->a[2])));
+        RUN(pool(st->a[2], st->p[1], 32, 96));
+        RUN((conv<S1, false>(c, s, st, dims(3, 48, 1), st->p[1], P + L.cw[2], P + L.cb[2], st->a[3])));
+        RUN(pool(st->a[3], st->p[2], 64, 48));
+        RUN((conv<S1, false>(c, s, st, dims(4, 24, 1), st->p[2], P + L.cw[3], P + L.cb[3], st->a[4])));
+        RUN(pool(st->a[4], st->p[3], 64, 24));
+        RUN((conv<S1, false>(c, s, st, dims(5, 12, 1), st->p[3], P + L.cw[4], P + L.cb[4], st->a[5])));
+        RUN(pool(st->a[5], st->p[4], 128, 12));
+        RUN((conv<S2P1, false>(c, s, st, dims(6, 6, 2), st->p[4], P + L.cw[5], P + L.cb[5], st->a[6])));
+    }
+    if (B <= kChainRows)      // the RL stage's batch: everything after the convolutions in one persistent launch
+        return chain_forward(c, s, st, P, image_feat, goal_sound_feat, rnn_hxs, masks, B, value, actor_features, logits, rnn_hxs_out);
+    return layer_forward(c, s, st, P, image_feat, goal_sound_feat, rnn_hxs, masks, B, value, actor_features, logits, rnn_hxs_out);
+}
+
+int var_ithor_policy_status(var_ctx* c, unsigned* word) {
+    if (!c) return VAR_ERR_ARG;
+    pol_state* st = (pol_state*)c->ipol;
+    if (!st || !word) { VAR_SET_ERR(c, "var_ithor_policy_status: var_ithor_policy_plan first"); return VAR_ERR_PLAN; }
+    VAR_HIP_CHECK(c, hipSetDevice(c->device));
+    return chain_status_word(c, st->sync, word);
+}
+
+int var_ithor_policy_clear_status(var_ctx* c) {
+    if (!c) return VAR_ERR_ARG;
+    pol_state* st = (pol_state*)c->ipol;
+    if (!st) { VAR_SET_ERR(c, "var_ithor_policy_clear_status: var_ithor_policy_plan first"); return VAR_ERR_PLAN; }
+    VAR_HIP_CHECK(c, hipSetDevice(c->device));
+    return chain_clear_status(c, st->sync);
+}
+
+}  // extern "C"
