@@ -192,7 +192,10 @@ int var_adam_step_graph(var_ctx* ctx, void* stream, float* params, const float* 
  * (processSoundFeat).  pcm: rows of `pcm_stride` int16 samples; output clip i reads row
  * clip_index[i] (NULL: row i) and lens[i] valid samples (<= pcm_stride; 0 = "empty" class =>
  * zeros); out: (nclips, 1, out_frames, 40) f32, frames beyond 1 + len/160 are zero
- * (MFCC-domain padding), frames beyond out_frames are dropped. */
+ * (MFCC-domain padding), frames beyond out_frames are dropped.  A clip of 1..256 samples is outside the domain of
+ * the reference (torch.stft's reflect padding needs more than n_fft / 2 samples): its 1 + len/160 rows are finite but
+ * pinned by no reference, the rows behind them zero; lens[i] > pcm_stride reads as pcm_stride.  More than 2^23
+ * output frames (nclips * out_frames) in one call are refused. */
 int var_mfcc(var_ctx* ctx, void* stream, const int16_t* pcm, const int* lens, const int* clip_index,
              int nclips, int pcm_stride, int out_frames, float* out);
 
@@ -344,7 +347,8 @@ int var_ithor_policy_clear_status(var_ctx* ctx);
  * .97, 400/160 frames with a zero-padded tail, np.hamming, |rfft_512|^2/512, 40 triangles, log, orthonormal DCT-II,
  * lifter 22, coefficient 0 = log frame energy; int16 samples NOT normalised) + processSoundFeat (:241-252).
  * Arguments as var_mfcc; T = 1 + ceil((len-400)/160) frames per clip (1 if len <= 400), out (nclips,1,out_frames,40)
- * f32 (the library computes float64; this kernel float32).  The tables are built on the first call (the only
+ * f32 (the library computes float64; this kernel float32).  pcm_stride must be even (rows are read as 4-byte sample
+ * pairs; an odd stride is refused with VAR_ERR_ARG, ops.mfcc_psf refuses an odd width).  The tables are built on the first call (the only
  * call of this entry that allocates: make it once outside graph capture). */
 int var_mfcc_psf(var_ctx* ctx, void* stream, const int16_t* pcm, const int* lens, const int* clip_index,
                  int nclips, int pcm_stride, int out_frames, float* out);

@@ -189,3 +189,223 @@ def mfcc_psf(signal, samplerate=16000, winlen=0.025, winstep=0.01, numcep=40, nf
     if append_energy:
         feat[:, 0] = np.log(energy)
     return feat
+
+
+# ---- edge-case signals and a conditioning-aware error bound (tests/test_oracle_mfcc.py, tests/test_gpu_mfcc_edges.py) ----
+# n_mfcc = n_mels = 40 and the DCT is orthonormal, so a float32 front-end's log-mel vector can be recovered on the host
+# (out @ dct_matrix().T) and compared where its conditioning is known: a quiet mel band next to a loud one is allowed
+# the FFT's error of the loud one, a loud band only its own rounding.
+EPS32 = 2.0 ** -24
+PAD_SAMPLE = 0x7FFF            # what the tests put behind lens[i] and into rows no clip names
+SIGNAL_KINDS = ("noise_tone", "tone440", "zeros", "const_max", "const_min", "nyquist", "impulse_first", "impulse_last",
+                "impulse_mid")
+TA_LENGTHS = (257, 258, 319, 320, 321, 400, 511, 512, 513, 15999, 16000, 12345)        # 512 / 400 / 160, T = 1 + N // 160
+PSF_LENGTHS = (1, 2, 399, 400, 401, 559, 560, 561, 720, 95999, 96000)                  # T = 1 + ceil((N - 400) / 160)
+EX_CONFIGS = ((64, 64, 16), (64, 33, 7), (128, 100, 128), (256, 256, 1), (1024, 800, 640), (2048, 2048, 512),
+              (2048, 1200, 2048))
+
+
+def ex_lengths(n_fft, win, hop):
+    """Clip lengths of one var_mfcc_ex configuration: the shortest clip the reflect padding accepts, a multiple of the
+    hop beyond one FFT frame and one sample either side of it ((256, 256, 1): one 600-sample clip, 601 frames)."""
+    if (n_fft, win, hop) == (256, 256, 1):
+        return (600,)
+    m = hop * (-(-(n_fft + hop) // hop))
+    return (n_fft // 2 + 1, m - 1, m, m + 1)
+
+
+def edge_signal(kind, n, seed=0):
+    """One int16 clip of n samples of the named class."""
+    x = np.zeros(n, dtype=np.int16)
+    if n <= 0:
+        return x
+    if kind == "noise_tone":
+        x[:] = synth_clips(1, seed=seed, n_samples=n)[0]
+    elif kind == "tone440":
+        x[:] = np.round(20000.0 * np.sin(2 * np.pi * 440.0 * np.arange(n) / 16000.0))
+    elif kind == "zeros":
+        pass
+    elif kind == "const_max":
+        x[:] = 32767
+    elif kind == "const_min":
+        x[:] = -32768
+    elif kind == "nyquist":
+        x[0::2] = 32767
+        x[1::2] = -32767
+    elif kind == "impulse_first":
+        x[0] = 32767
+    elif kind == "impulse_last":
+        x[n - 1] = -32767
+    elif kind == "impulse_mid":
+        x[n // 2] = 32767
+    else:
+        raise ValueError(kind)
+    return x
+
+
+def ta_frames(n, hop=HOP):
+    return 1 + n // hop if n > 0 else 0
+
+
+def psf_frames(n):
+    if n <= 0:
+        return 0
+    return 1 if n <= 400 else 1 + -(-(n - 400) // 160)
+
+
+def mfcc_torchaudio_parts(pcm, n_fft=N_FFT, win=WIN, hop=HOP):
+    """float64 MFCC of an int16 clip with the per-frame intermediates of the error bound:
+    P (T, n_freq) power, mel (T, 40), logmel (T, 40), R (T) = sqrt(n_fft) * ||x_t w||_2 >= every |X_k| of frame t."""
+    pcm = np.asarray(pcm)
+    assert pcm.dtype == np.int16
+    if pcm.shape[0] <= n_fft // 2:
+        raise ValueError("torch.stft(center=True, pad_mode='reflect') needs more than n_fft // 2 samples")
+    x = (pcm / 32768.0).astype(np.float32).astype(np.float64)
+    fr = frames_reflect(x, n_fft, hop) * padded_window(np.float64, n_fft, win)[None, :]
+    spec = np.fft.rfft(fr, n=n_fft, axis=1)
+    P = spec.real ** 2 + spec.imag ** 2
+    fb = mel_filterbank(n_fft=n_fft)
+    mel = P @ fb
+    logmel = np.log(mel + LOG_OFFSET)
+    return {"mfcc": logmel @ dct_matrix(), "P": P, "mel": mel, "logmel": logmel, "fb": fb,
+            "R": np.sqrt(n_fft) * np.sqrt(np.sum(fr * fr, axis=1))}
+
+
+def _matmul_f32(a, b):
+    """a @ b in float32, summed over the inner index in order (BLAS would pick an order per machine)."""
+    acc = np.zeros((a.shape[0], b.shape[1]), np.float32)
+    for k in range(a.shape[1]):
+        acc += a[:, k:k + 1] * b[k][None, :]
+    return acc
+
+
+def mfcc_torchaudio_f32(pcm, n_fft=N_FFT, win=WIN, hop=HOP):
+    """The same front-end with every stage in float32 (scipy's pocketfft keeps single precision): (T, 40) float32."""
+    from scipy import fft as sfft
+    f32 = np.float32
+    x = (np.asarray(pcm) / 32768.0).astype(f32)
+    fr = frames_reflect(x, n_fft, hop) * padded_window(f32, n_fft, win)[None, :]
+    spec = sfft.rfft(fr, n=n_fft, axis=1)
+    assert spec.dtype == np.complex64
+    P = spec.real * spec.real + spec.imag * spec.imag
+    mel = _matmul_f32(P, mel_filterbank(dtype=f32, n_fft=n_fft))
+    logmel = np.log(mel + f32(LOG_OFFSET))
+    out = _matmul_f32(logmel, dct_matrix(f32))
+    assert out.dtype == f32
+    return out
+
+
+def _power_bound(P, R, K):
+    # an FFT's error scales with the frame, not with the bin: d|X| <= K eps R, so dP <= 2 |X| d|X| + d|X|^2
+    return K * EPS32 * (2.0 * np.sqrt(P) * R[:, None] + EPS32 * R[:, None] ** 2)
+
+
+def logmel_bound(parts, K):
+    """First-order bound on |logmel_f32 - logmel_f64| per (frame, band), the float32 log-mel being recovered from the
+    float32 MFCC through the float64 inverse DCT."""
+    dP = _power_bound(parts["P"], parts["R"], K)
+    dmel = dP @ parts["fb"] + K * EPS32 * parts["mel"]
+    lm = parts["logmel"]
+    return (dmel / (parts["mel"] + LOG_OFFSET) + K * EPS32 * (1.0 + np.abs(lm))
+            + K * EPS32 * np.max(np.abs(lm), axis=1, keepdims=True))
+
+
+def recover_logmel(mfcc):
+    """(T, 40) MFCC of the torchaudio flavour -> its log-mel vector (the DCT matrix is orthogonal)."""
+    return np.asarray(mfcc, dtype=np.float64) @ dct_matrix().T
+
+
+def psf_lifter(numcep=40, L=22):
+    return 1.0 + (L / 2.0) * np.sin(np.pi * np.arange(numcep) / L)
+
+
+def mfcc_psf_parts(signal):
+    """mfcc_psf with the intermediates of its bound: P = |X|^2 / 512 (T, 257), mel (T, 40; exact zeros -> eps), logmel,
+    E (T; exact zeros -> eps), R = sqrt(512) * ||pre-emphasised, windowed frame||_2 (int16 units: nothing is normalised)."""
+    sig = np.asarray(signal).astype(np.float64)
+    sig = np.append(sig[0], sig[1:] - 0.97 * sig[:-1])
+    slen = len(sig)
+    T = psf_frames(slen)
+    padsignal = np.concatenate((sig, np.zeros(((T - 1) * 160 + 400 - slen,))))
+    frames = padsignal[np.arange(400)[None, :] + 160 * np.arange(T)[:, None]] * np.hamming(400)
+    spec = np.fft.rfft(frames, 512)
+    P = (spec.real ** 2 + spec.imag ** 2) / 512.0
+    E = np.sum(P, 1)
+    E = np.where(E == 0, np.finfo(float).eps, E)
+    fb = psf_filterbanks().T                                                     # (257, 40)
+    mel = P @ fb
+    mel = np.where(mel == 0, np.finfo(float).eps, mel)
+    logmel = np.log(mel)
+    out = (logmel @ dct_matrix()) * psf_lifter()
+    out[:, 0] = np.log(E)
+    return {"mfcc": out, "P": P, "mel": mel, "logmel": logmel, "E": E, "fb": fb,
+            "R": np.sqrt(512.0) * np.sqrt(np.sum(frames * frames, axis=1))}
+
+
+def mfcc_psf_f32(signal):
+    """The python_speech_features front-end with every stage in float32: (T, 40) float32."""
+    from scipy import fft as sfft
+    f32 = np.float32
+    sig = np.asarray(signal).astype(f32)
+    sig = np.append(sig[0], sig[1:] - f32(0.97) * sig[:-1]).astype(f32)
+    slen = len(sig)
+    T = psf_frames(slen)
+    padsignal = np.concatenate((sig, np.zeros(((T - 1) * 160 + 400 - slen,), f32)))
+    frames = padsignal[np.arange(400)[None, :] + 160 * np.arange(T)[:, None]] * np.hamming(400).astype(f32)
+    spec = sfft.rfft(frames, n=512, axis=1)
+    assert spec.dtype == np.complex64
+    P = (spec.real * spec.real + spec.imag * spec.imag) * f32(1.0 / 512.0)
+    E = np.sum(P, 1, dtype=f32)
+    E = np.where(E == 0, f32(np.finfo(float).eps), E)
+    mel = _matmul_f32(P, psf_filterbanks().T.astype(f32))
+    mel = np.where(mel == 0, f32(np.finfo(float).eps), mel)
+    out = _matmul_f32(np.log(mel), dct_matrix(f32)) * psf_lifter().astype(f32)
+    out[:, 0] = np.log(E)
+    assert out.dtype == f32
+    return out
+
+
+def psf_bounds(parts, K):
+    """(d_energy (T), d_coef (T, 39)): bounds on column 0 (log frame energy) and on the liftered coefficients 1..39 --
+    the log-mel bound pushed through |DCT| and the lifter (39 columns do not determine the log-mel vector)."""
+    dP = _power_bound(parts["P"] * 512.0, parts["R"], K) / 512.0
+    dmel = dP @ parts["fb"] + K * EPS32 * parts["mel"]
+    lm = parts["logmel"]
+    dlm = dmel / parts["mel"] + K * EPS32 * (1.0 + np.abs(lm)) + K * EPS32 * np.max(np.abs(lm), axis=1, keepdims=True)
+    d_coef = (dlm @ np.abs(dct_matrix())) * np.abs(psf_lifter())
+    d_en = K * EPS32 * (1.0 + np.abs(np.log(parts["E"]))) + np.sum(dP, axis=1) / parts["E"]
+    return d_en, d_coef[:, 1:]
+
+
+def k_ref_cases(flavour):
+    """Every (signal, length, configuration) of the edge table: 'ta' = torchaudio flavour (512 / 400 / 160 and the
+    var_mfcc_ex configurations), 'psf' = python_speech_features flavour."""
+    if flavour == "psf":
+        return [(k, n, None) for k in SIGNAL_KINDS for n in PSF_LENGTHS]
+    cfgs = [((N_FFT, WIN, HOP), TA_LENGTHS)] + [(c, ex_lengths(*c)) for c in EX_CONFIGS]
+    return [(k, n, c) for c, lens in cfgs for k in SIGNAL_KINDS for n in lens]
+
+
+def measure_k_ref(flavour):
+    """max over the edge table of |float32 restatement - float64 reference| / bound(K = 1), and the case it came from."""
+    worst, where = 0.0, None
+    for kind, n, cfg in k_ref_cases(flavour):
+        x = edge_signal(kind, n, seed=n)
+        if flavour == "psf":
+            parts = mfcc_psf_parts(x)
+            got = mfcc_psf_f32(x).astype(np.float64)
+            d_en, d_coef = psf_bounds(parts, 1.0)
+            r = max(np.max(np.abs(got[:, 0] - parts["mfcc"][:, 0]) / d_en),
+                    np.max(np.abs(got[:, 1:] - parts["mfcc"][:, 1:]) / d_coef))
+        else:
+            parts = mfcc_torchaudio_parts(x, *cfg)
+            got = recover_logmel(mfcc_torchaudio_f32(x, *cfg))
+            r = np.max(np.abs(got - parts["logmel"]) / logmel_bound(parts, 1.0))
+        if r > worst:
+            worst, where = float(r), (kind, n, cfg)
+    return worst, where
+
+
+if __name__ == "__main__":              # python -m oracle.mfcc_np
+    for fl in ("ta", "psf"):
+        print(fl, *measure_k_ref(fl))

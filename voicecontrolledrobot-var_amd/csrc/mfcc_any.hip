@@ -150,13 +150,17 @@ int launch_mfcc_any(var_ctx* c, hipStream_t s, const int16_t* pcm, const int* le
         VAR_SET_ERR(c, "var_mfcc_ex: n_fft %d (a power of two in 64..%d), win_length %d (<= n_fft), hop_length %d", n_fft, MAXFFT, win, hop);
         return VAR_ERR_ARG;
     }
+    const long total = (long)nclips * out_frames;
+    if (total > 0x7fffffffL) {                 // the kernel counts frames in an int
+        VAR_SET_ERR(c, "var_mfcc_ex: %d clips x %d frames is too many", nclips, out_frames);
+        return VAR_ERR_ARG;
+    }
     AnyTab& T = tabs()[std::make_tuple(c, n_fft, win, hop)];
     if (!T.dev) {
         int rc = build_any(c, n_fft, win, hop, T);
         if (rc != VAR_OK) return rc;
         if ((rc = retire_block(c, T.dev)) != VAR_OK) return rc;          // freed by var_destroy
     }
-    const long total = (long)nclips * out_frames;
     const int lds_bytes = (WAVES * n_fft * 2 + WAVES * 64) * 4;
     static unsigned attr_set = 0;      // bit d: set on device d (function attributes are per device)
     if (!(attr_set & var_dev_bit(c))) {
