@@ -343,6 +343,39 @@ int var_ithor_policy_forward(var_ctx* ctx, void* stream, const float* params, in
 int var_ithor_policy_status(var_ctx* ctx, unsigned* word);
 int var_ithor_policy_clear_status(var_ctx* ctx);
 
+/* The frozen iTHOR encoder's reward step at RL batch sizes -----------------------------------------------------------
+ * What the vectorised-env wrapper asks of the frozen pretext model on every environment step
+ * (Envs/vec_env/vec_pretext_normalize.py:82-101 getEmbeddings / calcReward, processAI2Thor :125-146): the image embedding,
+ * the goal sound's embedding (computed on the first step of an episode and cached FOR THE WHOLE BATCH afterwards,
+ * models/pretext/pretext_base.py:26-32 "assuming every env reset at the same time") and their row dot.  The model is
+ * models/pretext/ai2thor_pretext_model.py:5-58; params = the var_ithor_param_count() floats of var_ithor_encoder_fwd.
+ * Inference only and always fp32, whatever var_ithor_set_bf16 says; nothing of the training path (its workspace, its bf16 /
+ * GRU-sequence switches, its saved forward) is read or written, and a later var_plan / var_ithor_plan /
+ * var_ithor_policy_plan at any batch leaves a captured reward graph valid: the plan owns every buffer it uses.
+ *   var_ithor_reward_plan  (ai2thor_pretext_model.py:14-30: the 96x96 stack; Envs/ai2thor/RL_env_VAR.py:484 resizes to 96
+ *       unconditionally): img_hw must be 96 and 1 <= max_batch <= 64 (the band convolutions' limit), else VAR_ERR_ARG --
+ *       other sizes keep using var_ithor_encoder_fwd.  Only grows; a superseded block stays alive until var_destroy.
+ *   var_ithor_reward_pack  (the encoder is frozen, VAR/RL_VAR.py loads it once): copies the arena into the plan's memory
+ *       and lays conv 2..6 out for the matrix cores ONCE.  Every step reads that snapshot: parameters changed in place
+ *       afterwards (load_state_dict) take effect at the next pack, not before, and packing again is all a checkpoint load
+ *       needs -- the snapshot's address does not move, so captured graphs follow it.
+ *   var_ithor_reward_step  (pretext_base.py:10-41 + calcReward): image (B,3,96,96) u8 (divided by 255) or f32,
+ *       image_bstride >= 3*96*96 elements between images; goal_mfcc (B,1,600,40) or NULL.  With goal_mfcc: goal_feat (B,3)
+ *       is written; with NULL it is read (the cached embedding).  image_feat (B,3) and reward (B) = sum_d image_feat *
+ *       goal_feat are always written.  params must be the arena of the last pack (VAR_ERR_STATE otherwise, and before any
+ *       pack); VAR_ERR_PLAN before the plan or beyond its batch.  A failed call launches nothing.
+ * Launches (a captured step replays as this many kernel nodes): image only 7 (conv 1, four band convolutions with their
+ * pool, the stride-2 conv 6, one tail: both Linear layers, F.normalize and the dot); with a goal 7 + 3 convolutions + the
+ * input projection + 73 GRU steps (one launch each up to 16 clips: recurrent product of both directions, b_hh, gates and h'
+ * fused; two launches each beyond, 72 products) + the 3 Linear layers of the sound head.  No kernel waits for another
+ * workgroup: there is no time-out and no status word. */
+int var_ithor_reward_plan(var_ctx* ctx, int max_batch, int img_hw);
+int var_ithor_reward_pack(var_ctx* ctx, void* stream, const float* params);
+int var_ithor_reward_step(var_ctx* ctx, void* stream, const float* params,
+                          const void* image, int image_is_u8, long image_bstride,
+                          const float* goal_mfcc, int B,
+                          float* image_feat, float* goal_feat, float* reward);
+
 /* The iTHOR/FSC audio front-end: python_speech_features.mfcc as called at Envs/audioLoader.py:158-161 (pre-emphasis
  * .97, 400/160 frames with a zero-padded tail, np.hamming, |rfft_512|^2/512, 40 triangles, log, orthonormal DCT-II,
  * lifter 22, coefficient 0 = log frame energy; int16 samples NOT normalised) + processSoundFeat (:241-252).

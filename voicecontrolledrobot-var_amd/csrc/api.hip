@@ -82,6 +82,7 @@ int var_destroy(var_ctx* c) {
     ithor_free(c);
     armnet_free(c);
     ithor_policy_free(c);
+    ithor_reward_free(c);
     for (auto& sl : c->ws_slot) if (sl.base) (void)hipFree(sl.base);
     for (int i = 0; i < c->n_retired; i++) (void)hipFree(c->retired[i]);
     free(c->retired);

@@ -199,6 +199,7 @@ struct var_ctx {
     void* arm = nullptr;                  // actor-critic state (armnet.hip), created by var_armnet_plan
     void* ith = nullptr;                  // iTHOR model state (ithor.hip), created by var_ithor_plan
     void* ipol = nullptr;                 // iTHOR actor-critic state (ithor_policy.hip), created by var_ithor_policy_plan
+    void* irew = nullptr;                 // frozen iTHOR encoder's reward step (ithor_reward.hip), created by var_ithor_reward_plan
     const unsigned* adam_guard = nullptr; // device word: non-zero = the gradient of this step is invalid (a persistent GRU launch timed
     long adam_guard_n = 0;                // out): Adam launches over adam_guard_n parameters leave parameters, moments and step alone
     const float* adam_guard_loss = nullptr;   // device float (the step's -- under data parallelism the all-reduced -- loss): not finite = the same
@@ -308,6 +309,7 @@ void mfcc_any_forget(var_ctx* c);
 void ithor_free(var_ctx* c);
 void armnet_free(var_ctx* c);
 void ithor_policy_free(var_ctx* c);
+void ithor_reward_free(var_ctx* c);
 void comm_free(var_ctx* c);
 int pack_table_upload(var_ctx* c);
 size_t img_slab_floats();

@@ -75,7 +75,7 @@ class IntrinsicReward:
         goal = to(goal_sound)
         if goal is None:
             b = img.shape[0]
-            goal = torch.full((b, 1, 100, 40), float("inf"), device=dev)
+            goal = torch.full((b,) + tuple(self.model.config.sound_dim), float("inf"), device=dev)
         d = self.model(img, goal.float().contiguous(),
                        to(current_sound).float().contiguous() if (self.sound_sound and current_sound is not None) else None)
         image_feat = d["image_feat"].cpu().numpy()
@@ -88,9 +88,17 @@ class IntrinsicReward:
         """Capture the frozen encoder for a fixed number of envs (BASELINE config 5: 8) into two HIP graphs --
         image + goal sound (first step of an episode) and image only (later steps: the goal embedding is reused) --
         over static device buffers.  Weights are packed once here: call again after loading another checkpoint.
-        Returns self; then use step()."""
+        Returns self; then use step().
+
+        For an IthorVARPretextNet the step is var_ithor_reward_step (96 x 96 images, at most 64 envs): the arena is
+        snapshotted and its convolutions packed once here, so the graphs follow the weights the model had at this call
+        until capture() is called again.  The goal embedding is cached for the WHOLE batch (pretext_base.py:26-32:
+        every env resets at the same time); step(image, None) before any goal step raises."""
         from ._lib import Context, current_stream_handle, new_graph, ptr
         m = self.model
+        from .ithor import IthorVARPretextNet
+        if isinstance(m, IthorVARPretextNet):
+            return self._capture_ithor(batch)
         flat = m.flat_parameters()
         dev = flat.device
         c = Context.get(dev.index)
@@ -133,10 +141,79 @@ class IntrinsicReward:
         torch.cuda.current_stream().wait_stream(side)
         return self
 
+    def _capture_ithor(self, batch):
+        from ._lib import Context, VarHipError, current_stream_handle, new_graph, ptr
+        m = self.model
+        flat = m.flat_parameters()
+        dev = flat.device
+        if not flat.is_cuda:
+            raise VarHipError("IntrinsicReward.capture needs the model on the GPU (no CPU fallback)")
+        c = Context.get(dev.index)
+        if flat.numel() != c.lib.var_ithor_param_count():
+            raise VarHipError("parameter arena does not match var_ithor_param_count()")
+        hw = m.config.img_dim[1]
+        B = int(batch)
+        c.check(c.lib.var_ithor_reward_plan(c.handle, B, int(hw)), "var_ithor_reward_plan")
+        c.check(c.lib.var_ithor_reward_pack(c.handle, current_stream_handle(), ptr(flat)), "var_ithor_reward_pack")
+        self._B = B
+        self._ithor = True
+        self._have_goal = False
+        self._img = torch.zeros((B,) + tuple(m.config.img_dim), dtype=torch.uint8, device=dev)
+        self._goal = torch.zeros((B,) + tuple(m.config.sound_dim), dtype=torch.float32, device=dev)
+        self._image_feat = torch.zeros((B, 3), device=dev)
+        self._goal_feat = torch.zeros((B, 3), device=dev)
+        self._reward = torch.zeros((B,), device=dev)
+
+        def body(with_goal):
+            c.check(c.lib.var_ithor_reward_step(c.handle, current_stream_handle(), ptr(flat), ptr(self._img), 1,
+                                                self._img.stride(0), ptr(self._goal) if with_goal else None, B,
+                                                ptr(self._image_feat), ptr(self._goal_feat), ptr(self._reward)),
+                    "var_ithor_reward_step")
+
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        self._graphs = {}
+        with torch.cuda.stream(side):
+            for with_goal in (True, False):
+                body(with_goal)                                  # warm-up outside capture (lazy kernel attributes)
+                g = new_graph()
+                with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+                    body(with_goal)
+                self._graphs[with_goal] = g
+            self._goal_feat.zero_()                              # (the warm-up's embedding of the all-zero buffer is no goal)
+        torch.cuda.current_stream().wait_stream(side)
+        return self
+
+    def _step_ithor(self, image_u8, goal_sound):
+        from ._lib import VarHipError
+        image_u8 = torch.as_tensor(image_u8)
+        if not image_u8.is_cuda:
+            raise VarHipError("IntrinsicReward.step: image must be a CUDA tensor (no CPU fallback)")
+        if tuple(image_u8.shape) != tuple(self._img.shape):
+            raise VarHipError(f"IntrinsicReward.step: image shape {tuple(image_u8.shape)} is not {tuple(self._img.shape)}")
+        if goal_sound is not None:
+            goal_sound = torch.as_tensor(goal_sound)
+            if not goal_sound.is_cuda:
+                raise VarHipError("IntrinsicReward.step: goal_sound must be a CUDA tensor (no CPU fallback)")
+            if tuple(goal_sound.shape) != tuple(self._goal.shape):
+                raise VarHipError(f"IntrinsicReward.step: goal_sound shape {tuple(goal_sound.shape)} is not "
+                                  f"{tuple(self._goal.shape)}")
+        elif not self._have_goal:
+            raise VarHipError("IntrinsicReward.step: no goal embedding is cached yet -- pass goal_sound on the first "
+                              "step of an episode (pretext_base.py:26-32)")
+        self._img.copy_(image_u8, non_blocking=True)
+        if goal_sound is not None:
+            self._goal.copy_(goal_sound, non_blocking=True)
+            self._have_goal = True
+        self._graphs[goal_sound is not None].replay()
+        return self._image_feat, self._goal_feat, self._reward
+
     def step(self, image_u8, goal_sound=None):
         """One env step of `batch` envs: copies the observations into the static buffers and replays the graph.
         Returns device tensors (image_feat (B,3), goal_feat (B,3), <image_feat, goal_feat> (B,)); they are
         overwritten by the next step."""
+        if getattr(self, "_ithor", False):
+            return self._step_ithor(image_u8, goal_sound)
         self._img.copy_(torch.as_tensor(image_u8), non_blocking=True)
         if goal_sound is not None:
             self._goal.copy_(torch.as_tensor(goal_sound), non_blocking=True)
