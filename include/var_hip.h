@@ -343,6 +343,37 @@ int var_ithor_policy_forward(var_ctx* ctx, void* stream, const float* params, in
 int var_ithor_policy_status(var_ctx* ctx, unsigned* word);
 int var_ithor_policy_clear_status(var_ctx* ctx);
 
+/* The distribution tail of Policy.act -------------------------------------------------------------------------------
+ * What follows the forward in models/ppo/model.py:59-69: the action (dist.sample() or dist.mode()) and dist.log_probs(action)
+ * of DiagGaussian / Categorical (models/ppo/distributions.py:7-33, 60-84), ONE launch instead of about a dozen on (B,n)
+ * tensors; the entropy act() computes and discards is not computed.  fp32 throughout.
+ *   kind 0, DiagGaussian (1 <= n <= 4): head = action mean (B,n), logstd (n) (dist.logstd._bias); std = exp(logstd),
+ *       action f32 (B,n) = mean + std * z, or mean itself when deterministic (FixedNormal.mode);
+ *       logp (B,1) = sum_d( -(action - mean)^2 / (2 std^2) - logstd - 0.5 ln(2 pi) )  (torch.distributions.Normal.log_prob).
+ *   kind 1, Categorical (1 <= n <= 16): head = logits (B,n), logstd ignored; p = softmax(logits) with the row maximum
+ *       subtracted; action int64 (B,1) = the number of k in [0, n-1) with cdf_k <= u (inverse CDF: never above n - 1), or the
+ *       FIRST index of the largest logit when deterministic (FixedCategorical.mode); logp (B,1) = log_softmax(logits)[action].
+ * Noise.  noise_in given: the caller's values, z (B,n) for kind 0, u (B) for kind 1; rng_state is not touched.  noise_in NULL:
+ * Philox4x32-10 with key {rng_state[0], rng_state[1]} and counter {rng_state[2], rng_state[3], row, 0} -> words x0..x3 per row;
+ * u(x) = ((x >> 8) + 0.5) * 2^-24 evaluated in fp32 (exact below one half, round-to-even above: (0, 1], the largest word gives
+ * 1.0f); kind 1 takes u(x0); kind 0 takes Box-Muller pairs z0 = sqrt(-2 ln u(x0)) cos(2 pi u(x1)), z1 = ... sin, and z2, z3 from
+ * (x2, x3) the same way.  The 64-bit step {rng_state[2] low, rng_state[3] high} advances by one per launch, on the device (the
+ * last workgroup to arrive stores it; nothing waits for another workgroup): a captured graph draws fresh noise on every replay
+ * with no host write.  Launches that share one rng_state, and launches of more than one workgroup (B > 256, or a carry
+ * beyond 8192 floats) on one context, must be stream-ordered with each other (one arrival counter per context).  noise_out (same shape as noise_in, may be NULL) receives
+ * the noise used.  A deterministic launch reads no noise, writes no noise_out and leaves the step alone.
+ * Carry.  hxs_src given: the same launch also copies B * hidden floats to hxs_dst -- after var_*_forward wrote rnn_hxs_out, this
+ * puts it where the next forward reads rnn_hxs, so one static graph feeds its own next step (the forwards refuse in-place).
+ * VAR_ERR_ARG: B < 1, n out of range, kind not 0 / 1, NULL head / action / logp (/ logstd for kind 0), sampling with neither
+ * noise_in nor rng_state, hxs_src with NULL hxs_dst or hidden < 1, hxs_dst overlapping hxs_src.  A failed call launches
+ * nothing.  B is not bounded (rows are spread over workgroups of 256). */
+int var_policy_dist(var_ctx* ctx, void* stream, int kind /*0 DiagGaussian, 1 Categorical*/,
+                    const float* head /* (B,n): action mean | logits */, const float* logstd /* (n) | NULL */,
+                    int n, int B, int deterministic,
+                    const float* noise_in /* NULL = built-in generator */, unsigned* rng_state /* 4 words, device */,
+                    float* noise_out /* may be NULL */, void* action /* f32 (B,n) | int64 (B,1) */, float* logp /* (B,1) */,
+                    const float* hxs_src, float* hxs_dst, int hidden /* hxs_src NULL = no carry */);
+
 /* The frozen iTHOR encoder's reward step at RL batch sizes -----------------------------------------------------------
  * What the vectorised-env wrapper asks of the frozen pretext model on every environment step
  * (Envs/vec_env/vec_pretext_normalize.py:82-101 getEmbeddings / calcReward, processAI2Thor :125-146): the image embedding,

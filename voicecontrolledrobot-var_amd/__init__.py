@@ -11,7 +11,7 @@ from ._lib import VarHipError, build_library, library_path, load_library  # noqa
 from .layout import N_PARAMS, PARAM_SPECS  # noqa: F401
 from .model import VARPretextNet  # noqa: F401
 from .ithor import IthorTrainer, IthorVARPretextNet, project_representation  # noqa: F401
-from .actor_critic import ArmNetPolicy, IthorNetPolicy, Policy  # noqa: F401
+from .actor_critic import ActStep, ArmNetPolicy, IthorNetPolicy, Policy  # noqa: F401
 from .comm import RcclComm  # noqa: F401
 from .trainer import VARTrainer, train_representation, train_representation_from_pool, multistep_lr  # noqa: F401
 from .data import SyntheticTripletPool, TripletPool, choose_negative_id, load_wav_clips, process_sound_feat  # noqa: F401

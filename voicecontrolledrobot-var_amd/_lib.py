@@ -74,6 +74,7 @@ _SIGNATURES = {
     "var_ithor_policy_forward": (_i, [_vp, _vp, _vp, _i, _vp, _i, _l, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "var_ithor_policy_status": (_i, [_vp, _vp]),
     "var_ithor_policy_clear_status": (_i, [_vp]),
+    "var_policy_dist": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "var_ithor_reward_plan": (_i, [_vp, _i, _i]),
     "var_ithor_reward_pack": (_i, [_vp, _vp, _vp]),
     "var_ithor_reward_step": (_i, [_vp, _vp, _vp, _vp, _i, _l, _vp, _i, _vp, _vp, _vp]),

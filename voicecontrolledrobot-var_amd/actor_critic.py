@@ -4,6 +4,9 @@ keys (63 tensors -- the authors' RL checkpoints load unchanged), `act` / `get_va
 `recurrent_hidden_state_size`.  The forward (8 convolutions, 3 max pools, the MLPs, one GRU step, value head, actor
 trunk, DiagGaussian mean) is ONE C-ABI call, var_armnet_forward (csrc/armnet.hip); sampling and log-probabilities
 (a handful of flops on (B,2) tensors) use torch.distributions exactly as the reference's FixedNormal does.
+capture(num_envs) returns an ActStep: the same act() as ONE replayed HIP graph over static buffers -- the forward, then
+var_policy_dist (csrc/policy_dist.hip: sampling from a seeded on-device generator or the mode, the log-probabilities and
+the carry of the hidden state) -- for the RL loop's per-step latency; act() itself is unchanged.
 Inference only: evaluate_actions (the PPO update, models/ppo/algo/ppo.py) stays in PyTorch.  GPU only.
 
 IthorNetPolicy is the same for base 'ai2thor_VAR' (models/RL/ai2thor_RL_model.py:ai2thorNet_VAR, iTHOR configuration,
@@ -119,6 +122,120 @@ class _ArenaPolicy(nn.Module):
                                   "the reference Policy for training")
 
 
+class ActStep:
+    """One replayed Policy.act step over static device buffers, returned by ArmNetPolicy.capture / IthorNetPolicy.capture:
+    var_*_forward followed by var_policy_dist (sampling or mode, log-probabilities, and the copy that carries rnn_hxs_out
+    into the next step's rnn_hxs) captured into ONE HIP graph.
+
+        step = policy.capture(num_envs, seed=0)
+        value, action, action_log_probs, rnn_hxs = step(obs, masks)      # models/ppo/model.py:57-69
+
+    The returned tensors ARE the static buffers: the next step overwrites them (clone what a rollout keeps).  The hidden
+    state lives here: reset() zeroes or sets it, and a zero in `masks` resets that row inside the forward, as hxs * masks
+    does (models/ppo/model.py:118).  The noise comes from the kernel's own counter-based generator (include/var_hip.h),
+    keyed by `seed`, whose step advances on the device with every replay: the same seed gives the same action sequence;
+    the stream of numbers is not torch's, the distributions are the same.
+    obs, masks: the static input buffers; a tensor passed to step() that IS its buffer (the caller filled step.obs[...] in
+    place) is not copied.  head: the action mean (B,n) / the logits (B,n) of the last step; noise: the z (B,n) / u (B,) it
+    used; rng_step: the generator step it drew from (-1 before the first sampling step; reads the device, blocking).
+
+    Weights: the forwards re-pack their filters inside every call, so parameters updated IN PLACE (the PPO optimiser's
+    step, load_state_dict) are what the next replay computes with.  The graph holds the arena's address: after .to() /
+    .cuda() / anything else that moves the parameters, step() raises VarHipError -- call capture() again."""
+
+    def __init__(self, policy, batch, deterministic, seed, image_dtype):
+        if not policy._arena_intact():
+            policy._flatten_params()
+        flat = policy._flat
+        if not flat.is_cuda:
+            raise VarHipError(f"{type(policy).__name__}.capture needs the model on the GPU: call .to('cuda') (no CPU fallback)")
+        B, seed = int(batch), int(seed)
+        if B < 1 or not 0 <= seed < 1 << 64:
+            raise VarHipError("capture: batch must be >= 1 and seed in [0, 2^64)")
+        if image_dtype not in (torch.uint8, torch.float32):
+            raise VarHipError("capture: image_dtype is torch.uint8 (divided by 255 on the device) or torch.float32")
+        dev = flat.device
+        c = Context.get(dev.index)
+        policy._ensure_plan(c, B)
+        self.policy, self.batch, self.deterministic, self.seed = policy, B, bool(deterministic), seed
+        self._flat = flat                                         # (held: its address cannot be handed out again)
+        kind, n, hidden, logstd, shapes = policy._step_spec(B, image_dtype)
+        self.obs = {k: torch.zeros(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
+        f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)   # noqa: E731
+        self.masks, self._hxs, self._hout = f32(B, 1), f32(B, hidden), f32(B, hidden)
+        self.value, self.actor_features, self.head = f32(B, 1), f32(B, 128), f32(B, n)
+        self.action = f32(B, n) if kind == 0 else torch.zeros((B, 1), dtype=torch.int64, device=dev)
+        self.action_log_probs = f32(B, 1)
+        self.noise = f32(B, n) if kind == 0 else f32(B)
+        self._rng = torch.zeros(4, dtype=torch.int32, device=dev)
+        self._rng0 = torch.from_numpy(np.array([seed & 0xffffffff, seed >> 32, 0, 0], dtype=np.uint32).view(np.int32)).to(dev)
+
+        def body():
+            policy._launch_forward(c, self.obs, self._hxs, self.masks, self.value, self.actor_features, self.head, self._hout)
+            c.check(c.lib.var_policy_dist(c.handle, current_stream_handle(), kind, ptr(self.head), ptr(logstd), n, B,
+                                          int(self.deterministic), None, ptr(self._rng), ptr(self.noise), ptr(self.action),
+                                          ptr(self.action_log_probs), ptr(self._hout), ptr(self._hxs), hidden),
+                    "var_policy_dist")
+
+        from ._lib import new_graph
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            body()                                               # warm-up outside capture (lazy kernel attributes)
+            self._graph = new_graph()
+            with torch.cuda.graph(self._graph, stream=side, capture_error_mode="thread_local"):
+                body()
+            self._rng.copy_(self._rng0)                          # (the warm-up drew from step 0 and carried its state)
+            self._hxs.zero_()
+        torch.cuda.current_stream().wait_stream(side)
+
+    @property
+    def rng_step(self):
+        w = self._rng.cpu().numpy().view(np.uint32)
+        return ((int(w[3]) << 32) | int(w[2])) - 1
+
+    @torch.no_grad()
+    def reset(self, rnn_hxs=None):
+        """Zero the carried hidden state, or set it to rnn_hxs (B, recurrent_hidden_state_size)."""
+        if rnn_hxs is None:
+            self._hxs.zero_()
+        else:
+            self._hxs.copy_(self._checked(rnn_hxs, self._hxs, "rnn_hxs"), non_blocking=True)
+
+    @staticmethod
+    def _checked(t, buf, name):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise VarHipError(f"ActStep: {name} must be a CUDA tensor (no CPU fallback)")
+        if tuple(t.shape) != tuple(buf.shape):
+            raise VarHipError(f"ActStep: {name} has shape {tuple(t.shape)}, the captured step takes {tuple(buf.shape)}")
+        if (buf.dtype == torch.uint8) != (t.dtype == torch.uint8):
+            raise VarHipError(f"ActStep: {name} is {t.dtype}, the step was captured for {buf.dtype} (capture(image_dtype=...))")
+        return t
+
+    @torch.no_grad()
+    def step(self, obs, masks):
+        """Copy obs (the dict act() takes, CUDA tensors) and masks (B,1) into the static buffers and replay:
+        (value, action, action_log_probs, rnn_hxs), each overwritten by the next step."""
+        pol = self.policy
+        if pol._flat is not self._flat or not pol._arena_intact():
+            raise VarHipError("ActStep: the policy's parameter arena has moved since capture() (.to(), re-flattened "
+                              "parameters): call capture() again")
+        missing = [k for k in self.obs if k not in obs]
+        if missing:
+            raise VarHipError(f"ActStep: obs lacks {missing}")
+        src = {k: self._checked(obs[k], buf, k) for k, buf in self.obs.items()}
+        m = self._checked(masks, self.masks, "masks")
+        for k, buf in self.obs.items():
+            if src[k] is not buf:
+                buf.copy_(src[k], non_blocking=True)
+        if m is not self.masks:
+            self.masks.copy_(m, non_blocking=True)
+        self._graph.replay()
+        return self.value, self.action, self.action_log_probs, self._hout
+
+    __call__ = step
+
+
 class ArmNetPolicy(_ArenaPolicy):
     def __init__(self, obs_shape, action_space, config=None, base='arm_VAR', base_kwargs=None):
         super().__init__()
@@ -153,13 +270,9 @@ class ArmNetPolicy(_ArenaPolicy):
         if not flat.is_cuda:
             raise VarHipError("ArmNetPolicy runs on the GPU only: call .to('cuda') (no CPU fallback)")
         c = Context.get(flat.device.index)
-        if flat.numel() != c.lib.var_armnet_param_count():
-            raise VarHipError("parameter arena does not match var_armnet_param_count()")
         image = inputs['image']
         B = image.shape[0]
-        if self._plan < B:
-            c.check(c.lib.var_armnet_plan(c.handle, int(B)), "var_armnet_plan")
-            self._plan = B
+        self._ensure_plan(c, B)
         f32 = lambda t, shape: self._prep(t, shape)           # noqa: E731
         if not image.is_cuda:
             raise VarHipError("inputs must be CUDA tensors (no CPU fallback)")
@@ -174,11 +287,35 @@ class ArmNetPolicy(_ArenaPolicy):
         feats = torch.empty((B, 128), dtype=torch.float32, device=dev)
         mean = torch.empty((B, 2), dtype=torch.float32, device=dev)
         hout = torch.empty((B, 512), dtype=torch.float32, device=dev)
-        c.check(c.lib.var_armnet_forward(c.handle, current_stream_handle(), ptr(flat), ptr(image),
-                                         int(image.dtype == torch.uint8), image.stride(0), ptr(feat), ptr(pose), ptr(goal),
-                                         ptr(hxs), ptr(m), B, ptr(value), ptr(feats), ptr(mean), ptr(hout)),
-                "var_armnet_forward")
+        self._launch_forward(c, {'image': image, 'image_feat': feat, 'robot_pose': pose, 'goal_sound_feat': goal}, hxs, m,
+                             value, feats, mean, hout)
         return value, feats, mean, hout
+
+    def _ensure_plan(self, c, B):
+        if self._flat.numel() != c.lib.var_armnet_param_count():
+            raise VarHipError("parameter arena does not match var_armnet_param_count()")
+        if self._plan < B:
+            c.check(c.lib.var_armnet_plan(c.handle, int(B)), "var_armnet_plan")
+            self._plan = B
+
+    def _launch_forward(self, c, obs, hxs, masks, value, feats, mean, hout):
+        """The C call on prepared tensors (contiguous, on the arena's device)."""
+        image, B = obs['image'], obs['image'].shape[0]
+        c.check(c.lib.var_armnet_forward(c.handle, current_stream_handle(), ptr(self._flat), ptr(image),
+                                         int(image.dtype == torch.uint8), image.stride(0), ptr(obs['image_feat']),
+                                         ptr(obs['robot_pose']), ptr(obs['goal_sound_feat']), ptr(hxs), ptr(masks), B,
+                                         ptr(value), ptr(feats), ptr(mean), ptr(hout)),
+                "var_armnet_forward")
+
+    def _step_spec(self, B, image_dtype):
+        f = torch.float32
+        return 0, 2, 512, self.dist.logstd._bias, {'image': ((B, 3, 96, 96), image_dtype), 'image_feat': ((B, 3), f),
+                                                   'robot_pose': ((B, 2), f), 'goal_sound_feat': ((B, 3), f)}
+
+    def capture(self, batch, deterministic=False, seed=0, image_dtype=torch.uint8):
+        """act() for a fixed number of envs as one replayed HIP graph with on-device sampling: see ActStep.  image_dtype:
+        what 'image' will be fed as (uint8, or float32 already divided by 255)."""
+        return ActStep(self, batch, deterministic, seed, image_dtype)
 
     def chain_status(self):
         """Status of the small-batch (B <= 8) MLP chain launch, a persistent kernel that needs its 128 workgroups resident at
@@ -309,15 +446,11 @@ class IthorNetPolicy(_ArenaPolicy):
         if not flat.is_cuda:
             raise VarHipError("IthorNetPolicy runs on the GPU only: call .to('cuda') (no CPU fallback)")
         c = Context.get(flat.device.index)
-        if flat.numel() != c.lib.var_ithor_policy_param_count(self.n_actions):
-            raise VarHipError("parameter arena does not match var_ithor_policy_param_count()")
         image = inputs['image']
         B = image.shape[0]
         image = self._prep_u8(image, (B, 3, 96, 96))
         occ = self._prep_u8(inputs['occupancy'], (B, 1, 9, 9))
-        if self._plan < B:
-            c.check(c.lib.var_ithor_policy_plan(c.handle, int(B)), "var_ithor_policy_plan")
-            self._plan = B
+        self._ensure_plan(c, B)
         feat, goal = self._prep(inputs['image_feat'], (B, 3)), self._prep(inputs['goal_sound_feat'], (B, 3))
         hxs, m = self._prep(rnn_hxs, (B, 1024)), self._prep(masks, (B, 1))
         dev = flat.device
@@ -325,12 +458,37 @@ class IthorNetPolicy(_ArenaPolicy):
         feats = torch.empty((B, 128), dtype=torch.float32, device=dev)
         out_logits = torch.empty((B, self.n_actions), dtype=torch.float32, device=dev) if logits else None
         hout = torch.empty((B, 1024), dtype=torch.float32, device=dev)
-        c.check(c.lib.var_ithor_policy_forward(c.handle, current_stream_handle(), ptr(flat), self.n_actions, ptr(image),
-                                               int(image.dtype == torch.uint8), image.stride(0), ptr(occ),
-                                               int(occ.dtype == torch.uint8), ptr(feat), ptr(goal), ptr(hxs), ptr(m), B,
-                                               ptr(value), ptr(feats), ptr(out_logits), ptr(hout)),
-                "var_ithor_policy_forward")
+        self._launch_forward(c, {'image': image, 'occupancy': occ, 'image_feat': feat, 'goal_sound_feat': goal}, hxs, m,
+                             value, feats, out_logits, hout)
         return value, feats, out_logits, hout
+
+    def _ensure_plan(self, c, B):
+        if self._flat.numel() != c.lib.var_ithor_policy_param_count(self.n_actions):
+            raise VarHipError("parameter arena does not match var_ithor_policy_param_count()")
+        if self._plan < B:
+            c.check(c.lib.var_ithor_policy_plan(c.handle, int(B)), "var_ithor_policy_plan")
+            self._plan = B
+
+    def _launch_forward(self, c, obs, hxs, masks, value, feats, logits, hout):
+        """The C call on prepared tensors (contiguous, on the arena's device)."""
+        image, occ, B = obs['image'], obs['occupancy'], obs['image'].shape[0]
+        c.check(c.lib.var_ithor_policy_forward(c.handle, current_stream_handle(), ptr(self._flat), self.n_actions, ptr(image),
+                                               int(image.dtype == torch.uint8), image.stride(0), ptr(occ),
+                                               int(occ.dtype == torch.uint8), ptr(obs['image_feat']),
+                                               ptr(obs['goal_sound_feat']), ptr(hxs), ptr(masks), B,
+                                               ptr(value), ptr(feats), ptr(logits), ptr(hout)),
+                "var_ithor_policy_forward")
+
+    def _step_spec(self, B, image_dtype):
+        f = torch.float32
+        return 1, self.n_actions, 1024, None, {'image': ((B, 3, 96, 96), image_dtype), 'occupancy': ((B, 1, 9, 9), image_dtype),
+                                               'image_feat': ((B, 3), f), 'goal_sound_feat': ((B, 3), f)}
+
+    def capture(self, batch, deterministic=False, seed=0, image_dtype=torch.uint8):
+        """act() for a fixed number of envs as one replayed HIP graph with on-device sampling: see ActStep.  image_dtype:
+        what 'image' and 'occupancy' will be fed as (uint8, or float32 already divided by 255).  'image_feat' and
+        'goal_sound_feat' may be the device tensors IntrinsicReward.step returned: no host round trip."""
+        return ActStep(self, batch, deterministic, seed, image_dtype)
 
     def chain_status(self):
         """As ArmNetPolicy.chain_status, for this policy's small-batch (B <= 8) chain launch."""

@@ -162,6 +162,7 @@ struct var_ctx {
     float* ghid = nullptr;        // (3B,128)
     void* pack_segs_dev = nullptr; int pack_nseg = 0;   // pack segment table in device memory (pack_adam.hip)
     unsigned* done_ctr = nullptr; // self-resetting block counter of the graph-replayed Adam kernel
+    unsigned* dist_ctr = nullptr; // the same for var_policy_dist's launches of more than one workgroup (policy_dist.hip)
     // Device-side hand-over between the two streams of a training step (heads.hip, join_signal below): [0] arrivals of the sound
     // heads' forward workgroups, [1] completed launches of that kernel, [2] how many of them the caller's stream has waited for,
     // [3] waits for it that timed out (sticky; var_join_status); [4..7] the same for the conv 3-5 kernel and the side stream
