@@ -374,6 +374,83 @@ int var_policy_dist(var_ctx* ctx, void* stream, int kind /*0 DiagGaussian, 1 Cat
                     float* noise_out /* may be NULL */, void* action /* f32 (B,n) | int64 (B,1) */, float* logp /* (B,1) */,
                     const float* hxs_src, float* hxs_dst, int hidden /* hxs_src NULL = no carry */);
 
+/* The PPO rollout around the networks: storage, returns, loss head --------------------------------------------------------
+ * What models/ppo/storage.py and the loss lines of models/ppo/algo/ppo.py:38-87 do with dozens to hundreds of launches on
+ * (N,1) / (T*N,1) tensors, as three entries of ONE launch each.  The networks' evaluation forward and backward stay with the
+ * caller (PyTorch autograd).  fp32; no entry waits for another workgroup, allocates or synchronises.
+ *
+ * var_rollout_move: one strided row copy.  `segs` is a HOST array of 1..VAR_MOVE_MAX_SEGS segments (it travels to the kernel
+ * by value: nothing is read from it after the call returns).  For every segment, every t < n_t and every j < n_env,
+ *     e = ind ? ind[j] : j;   row_bytes bytes go from  src + t * src_t_stride + e * src_env_stride
+ *                                               to    dst + t * dst_t_stride + j * dst_env_stride      (strides in bytes).
+ * ind: device int32 (n_env) or NULL; n_src_env: the envs the source holds -- a row whose index lies outside [0, n_src_env) is
+ * left unwritten (the list lives on the device: the host cannot refuse it).  dtype-blind: 16-byte pieces when both ends,
+ * row_bytes and all four strides of a segment are multiples of 16, 4-byte words when of 4, bytes otherwise.  Uses:
+ *   RolloutStorage.insert (storage.py:61-77): n_t = 1, destinations slot step + 1 of obs / hidden states / masks / bad_masks and
+ *       slot step of actions / log-probs / value_preds / rewards;
+ *   after_update (:79-87): slot T -> slot 0;
+ *   one minibatch of recurrent_generator (:173-245): n_t = T, ind = the minibatch's envs, dst_t_stride = Nb * row_bytes,
+ *       dst_env_stride = row_bytes: output row t * Nb + j, _flatten_helper's (T, Nb) -> T * Nb; the hidden state is a
+ *       further segment with n_t = 1 reading slot 0.
+ * VAR_ERR_ARG: no / too many segments, NULL end, row_bytes / n_t / n_env / n_src_env < 1, a negative stride, n_env > n_src_env
+ * without ind, destination rows of a segment that overlap each other (dst_env_stride < row_bytes, or dst_t_stride smaller
+ * than a step's rows), a destination range -- first to last byte a segment may touch -- that overlaps any segment's source
+ * range or another segment's destination range, more than 2^31 - 1 workgroups.  A failed call launches nothing.
+ *
+ * var_rollout_returns: compute_returns (storage.py:89-128) in all four modes and the advantage normalisation of
+ * ppo.py:39-41, one workgroup.  rewards (T,N,1), value_preds / masks / bad_masks / returns (T+1,N,1), next_value (N,1),
+ * advantages (T,N,1) or NULL.  bad_masks may be NULL without use_proper_time_limits.  GAE stores value_preds[T] = next_value,
+ * the other mode returns[T] = next_value, as the reference.  With g = (float)gamma, gl = (float)(gamma * gae_lambda) (product
+ * in double), per env, t = T-1 .. 0, each operation rounded to fp32 in this grouping (bit-equal to the reference on the CPU):
+ *   GAE:          d = (r[t] + (g * v[t+1]) * m[t+1]) - v[t];  a = d + (gl * m[t+1]) * a;  proper: a = a * bm[t+1];  ret[t] = a + v[t]
+ *   else, proper: ret[t] = ((ret[t+1] * g) * m[t+1] + r[t]) * bm[t+1] + (1 - bm[t+1]) * v[t]
+ *   else:         ret[t] = (ret[t+1] * g) * m[t+1] + r[t]
+ * advantages = (A - mean(A)) / (std(A) + 1e-5), A = ret[:T] - v[:T], std unbiased (T*N - 1), two passes (mean, then squared
+ * deviations), summed in a fixed order: equal inputs give equal bits.  Envs beyond the workgroup's 256 threads are looped.
+ * VAR_ERR_ARG: T or N < 1, a NULL pointer, advantages with T * N < 2 (no standard deviation), an output overlapping an input
+ * or the other output.  A failed call launches nothing.
+ *
+ * var_ppo_head: the loss of ppo.py:66-87 for one minibatch of M rows and its gradients.  kind / n / head / logstd as
+ * var_policy_dist; value, old_logp, adv, returns, value_preds (M,1); action f32 (M,n) | int64 (M,1) (a Categorical action
+ * outside [0, n) gives NaN losses, never a read outside the row).  out[4] = {value_loss, action_loss, dist_entropy, total},
+ * total = value_loss * value_coef + action_loss - dist_entropy * entropy_coef; g_head (M,n), g_value (M,1), g_logstd (n, kind 0;
+ * may be NULL for kind 1) = d total / d head, value, logstd.  value_preds may be NULL without use_clipped_value_loss.
+ * logp (M,1), may be NULL: the log-probabilities of `action` the ratio was taken from.
+ *   logp: Gaussian sum_d( -(a - mu)^2 / (2 sigma^2) - logstd - 0.5 ln 2 pi ), Categorical log_softmax(head)[a];
+ *   ratio = exp(logp - old_logp); action_loss = -mean(min(ratio * adv, clamp(ratio, 1 - clip, 1 + clip) * adv));
+ *   value_loss = 0.5 mean(max((v - ret)^2, (vpc - ret)^2)), vpc = vp + clamp(v - vp, -clip, clip), or 0.5 mean((ret - v)^2);
+ *   dist_entropy = dist.entropy().mean() (models/ppo/model.py:80): Gaussian, over M * n elements of 0.5 + 0.5 ln 2 pi +
+ *   logstd_d; Categorical, over M rows of -sum_k p_k ln p_k.
+ * Gradients at the kinks are autograd's:
+ *   d action_loss / d logp = -adv * ratio / M where ratio * adv <= clamp(ratio) * adv, 0 elsewhere (torch.min splits a tie in
+ *       halves and clamp's mask includes its ends: a tie is inside the clip range, where the halves add up, or has adv = 0);
+ *   clipped value loss, l1 = (v - ret)^2, l2 = (vpc - ret)^2: weights (1,0) / (0,1) / (1/2,1/2) for l1 > / < / = l2, the l2
+ *       branch passing only where |v - vp| <= clip:  d value_loss / d v = (w1 (v - ret) + w2 [|v - vp| <= clip] (vpc - ret)) / M;
+ *   d logp / d l_k = [k = a] - p_k;  d logp / d mu_d = (a - mu) / sigma^2;  d logp / d logstd_d = (a - mu)^2 / sigma^2 - 1;
+ *   d H_row / d l_k = -p_k (ln p_k + H_row);  d dist_entropy / d logstd_d = 1 / n.
+ * The sums over rows (the three losses, g_logstd): rows are spread over at most 256 workgroups, each leaves partial sums in the
+ * context, the last one to arrive folds them in a fixed order -- equal inputs give equal bits, nothing waits, M is not bounded.
+ * Launches of more than one workgroup (M > 256) on one context must be stream-ordered with each other.
+ * VAR_ERR_ARG: kind not 0 / 1, M < 1, n out of range, clip < 0 or NaN, a NULL pointer other than those named above.  A failed
+ * call launches nothing. */
+#define VAR_MOVE_MAX_SEGS 16
+typedef struct var_move_seg {
+    const void* src;
+    void* dst;
+    long row_bytes, n_t;
+    long src_t_stride, dst_t_stride, src_env_stride, dst_env_stride;
+} var_move_seg;
+int var_rollout_move(var_ctx* ctx, void* stream, const var_move_seg* segs /* host */, int n_seg,
+                     const int* ind /* device (n_env) | NULL */, int n_env, int n_src_env);
+int var_rollout_returns(var_ctx* ctx, void* stream, const float* rewards, float* value_preds, const float* masks,
+                        const float* bad_masks, const float* next_value, int T, int N, int use_gae, double gamma,
+                        double gae_lambda, int use_proper_time_limits, float* returns, float* advantages /* may be NULL */);
+int var_ppo_head(var_ctx* ctx, void* stream, int kind /*0 DiagGaussian, 1 Categorical*/, const float* head, const float* logstd,
+                 const float* value, const void* action, const float* old_logp, const float* adv, const float* returns,
+                 const float* value_preds, int n, long M, float clip, float value_coef, float entropy_coef,
+                 int use_clipped_value_loss, float* out /* 4 */, float* g_head, float* g_value, float* g_logstd,
+                 float* logp /* (M,1), may be NULL */);
+
 /* The frozen iTHOR encoder's reward step at RL batch sizes -----------------------------------------------------------
  * What the vectorised-env wrapper asks of the frozen pretext model on every environment step
  * (Envs/vec_env/vec_pretext_normalize.py:82-101 getEmbeddings / calcReward, processAI2Thor :125-146): the image embedding,

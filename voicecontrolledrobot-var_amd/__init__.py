@@ -17,3 +17,4 @@ from .trainer import VARTrainer, train_representation, train_representation_from
 from .data import SyntheticTripletPool, TripletPool, choose_negative_id, load_wav_clips, process_sound_feat  # noqa: F401
 from .ops import inbatch_contrastive_loss, mfcc, mfcc_psf, triplet_margin_loss  # noqa: F401
 from .reward import IntrinsicReward, ReturnNormalizer, RunningMeanStd  # noqa: F401
+from .rollout import PPO, RolloutStorage, ppo_loss  # noqa: F401

@@ -29,7 +29,14 @@ def build_library(force=False):
     return _LIB_PATH
 
 
-_vp, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
+_vp, _i, _l, _f, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
+
+
+class MoveSeg(ctypes.Structure):
+    """var_move_seg of include/var_hip.h (var_rollout_move's segment table, a host array)."""
+    _fields_ = [("src", _vp), ("dst", _vp), ("row_bytes", _l), ("n_t", _l), ("src_t_stride", _l), ("dst_t_stride", _l),
+                ("src_env_stride", _l), ("dst_env_stride", _l)]
+
 
 _SIGNATURES = {
     "var_init": (_i, [_i, ctypes.POINTER(_vp)]),
@@ -75,6 +82,9 @@ _SIGNATURES = {
     "var_ithor_policy_status": (_i, [_vp, _vp]),
     "var_ithor_policy_clear_status": (_i, [_vp]),
     "var_policy_dist": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "var_rollout_move": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i]),
+    "var_rollout_returns": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _d, _d, _i, _vp, _vp]),
+    "var_ppo_head": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _l, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "var_ithor_reward_plan": (_i, [_vp, _i, _i]),
     "var_ithor_reward_pack": (_i, [_vp, _vp, _vp]),
     "var_ithor_reward_step": (_i, [_vp, _vp, _vp, _vp, _i, _l, _vp, _i, _vp, _vp, _vp]),

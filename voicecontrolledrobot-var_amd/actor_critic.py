@@ -7,7 +7,8 @@ trunk, DiagGaussian mean) is ONE C-ABI call, var_armnet_forward (csrc/armnet.hip
 capture(num_envs) returns an ActStep: the same act() as ONE replayed HIP graph over static buffers -- the forward, then
 var_policy_dist (csrc/policy_dist.hip: sampling from a seeded on-device generator or the mode, the log-probabilities and
 the carry of the hidden state) -- for the RL loop's per-step latency; act() itself is unchanged.
-Inference only: evaluate_actions (the PPO update, models/ppo/algo/ppo.py) stays in PyTorch.  GPU only.
+Inference only: evaluate_actions raises -- the PPO update is var_amd.PPO (rollout.py) over the reference Policy, whose
+evaluation forward and backward stay in PyTorch autograd.  GPU only.
 
 IthorNetPolicy is the same for base 'ai2thor_VAR' (models/RL/ai2thor_RL_model.py:ai2thorNet_VAR, iTHOR configuration,
 Discrete actions: 64 tensors, var_ithor_policy_forward in csrc/ithor_policy.hip, sampling through
@@ -118,8 +119,9 @@ class _ArenaPolicy(nn.Module):
         return t
 
     def evaluate_actions(self, inputs, rnn_hxs, masks, action):
-        raise NotImplementedError("the PPO update (models/ppo/algo/ppo.py) stays in PyTorch: load this state_dict into "
-                                  "the reference Policy for training")
+        raise NotImplementedError("the networks' evaluation forward and backward stay in PyTorch: load this state_dict into "
+                                  "the reference Policy and train it with var_amd.PPO over var_amd.RolloutStorage (storage, "
+                                  "returns and the PPO loss head run on the device)")
 
 
 class ActStep:
