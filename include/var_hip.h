@@ -451,6 +451,41 @@ int var_ppo_head(var_ctx* ctx, void* stream, int kind /*0 DiagGaussian, 1 Catego
                  int use_clipped_value_loss, float* out /* 4 */, float* g_head, float* g_value, float* g_logstd,
                  float* logp /* (M,1), may be NULL */);
 
+/* The PPO update's recurrent sequence, forward and backward --------------------------------------------------------------
+ * NNBase._forward_gru (models/ppo/model.py:116-171) of a one-layer, one-direction nn.GRU with biases, as PPO.update
+ * (models/ppo/algo/ppo.py:55-58 -> Policy.evaluate_actions, model.py:75-83) runs it on every minibatch: x (T*N, I), hxs (N, H),
+ * masks (T*N, 1), w_ih (3H, I), w_hh (3H, H), b_ih (3H), b_hh (3H) in nn.GRU's layout and gate order r, z, n.  For t = 0..T-1,
+ * h_{-1} = hxs:
+ *     h' = h_{t-1} * m_t (row-wise);  gi = W_ih x_t + b_ih;  gh = W_hh h' + b_hh
+ *     r = s(gi_r + gh_r), z = s(gi_z + gh_z), n = tanh(gi_n + r * gh_n), h_t = (1 - z) * n + z * h'
+ * out (T*N, H) = every h_t, h_T (N, H) = h_{T-1}.  For 0/1 masks this IS the reference's segmented form (model.py:132-166: it
+ * multiplies all rows by masks[t] at every step where some row is 0, and at the other steps every mask is 1.0) without the
+ * device-to-host read of the zero steps (model.py:134-138); T = 1 is its single-step branch (model.py:117-120).  Other mask
+ * values are multiplied in as they are, which the reference does not do.  fp32.  Step t's result does not depend on T: T
+ * chained one-step calls fed with their own h_T give the bits of one T-step call.
+ *   var_gru_seq_workspace_bytes  bytes of `workspace` either direction needs at this shape (VAR_ERR_ARG for a refused shape).
+ *   var_gru_seq_fwd  1 + T launches (input projection, one per step).  saved: 5*T*N*H floats (r | z | n | gh_n | h', each
+ *       (T*N, H)) for the backward, or NULL when nobody differentiates.  The workspace holds gi.
+ *   var_gru_seq_bwd  (what autograd replays for model.py:116-171) given d_out (T*N, H) and d_hT (N, H) or NULL: d_x (T*N, I),
+ *       d_hxs (N, H: what flows past m_0), d_w_ih, d_w_hh, d_b_ih, d_b_hh; masks carry no gradient.  x, masks, w_ih, w_hh as
+ *       in the forward whose `saved` is passed.  One launch transposes w_hh into the workspace (per call: an optimiser moves the
+ *       weights between two minibatches, nothing packed is kept), T + 1 step launches walk t downwards, then the batched
+ *       products (split-K slabs in the workspace, added in slab order) and the bias column sums: no atomics, equal inputs give
+ *       equal bits.  The gradients are stored, not accumulated.
+ * Both are stream-ordered on `stream`, never synchronise, never allocate: every buffer is the caller's.  VAR_ERR_ARG, with a
+ * message and nothing launched: H not a multiple of 64 or above 1024, I outside 1..1024, N outside 1..64, T < 1 (or T*N*3H
+ * above 2^30), a workspace smaller than var_gru_seq_workspace_bytes, out overlapping x or hxs (h_T, saved and the workspace
+ * may not overlap out or hxs either), a NULL pointer other than saved / d_hT, hxs / w_hh / out / saved / workspace not
+ * 16-byte aligned.  No kernel waits for another workgroup: there is no time-out and no status word. */
+long var_gru_seq_workspace_bytes(int T, int N, int I, int H);
+int var_gru_seq_fwd(var_ctx* ctx, void* stream, const float* x, const float* hxs, const float* masks, const float* w_ih,
+                    const float* w_hh, const float* b_ih, const float* b_hh, int T, int N, int I, int H, float* out,
+                    float* h_T, float* saved /* may be NULL */, void* workspace, long workspace_bytes);
+int var_gru_seq_bwd(var_ctx* ctx, void* stream, const float* x, const float* masks, const float* w_ih, const float* w_hh,
+                    const float* saved, const float* d_out, const float* d_hT /* may be NULL */, int T, int N, int I, int H,
+                    float* d_x, float* d_hxs, float* d_w_ih, float* d_w_hh, float* d_b_ih, float* d_b_hh, void* workspace,
+                    long workspace_bytes);
+
 /* The frozen iTHOR encoder's reward step at RL batch sizes -----------------------------------------------------------
  * What the vectorised-env wrapper asks of the frozen pretext model on every environment step
  * (Envs/vec_env/vec_pretext_normalize.py:82-101 getEmbeddings / calcReward, processAI2Thor :125-146): the image embedding,

@@ -85,6 +85,9 @@ _SIGNATURES = {
     "var_rollout_move": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i]),
     "var_rollout_returns": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _d, _d, _i, _vp, _vp]),
     "var_ppo_head": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _l, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+    "var_gru_seq_workspace_bytes": (_l, [_i, _i, _i, _i]),
+    "var_gru_seq_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _l]),
+    "var_gru_seq_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l]),
     "var_ithor_reward_plan": (_i, [_vp, _i, _i]),
     "var_ithor_reward_pack": (_i, [_vp, _vp, _vp]),
     "var_ithor_reward_step": (_i, [_vp, _vp, _vp, _vp, _i, _l, _vp, _i, _vp, _vp, _vp]),

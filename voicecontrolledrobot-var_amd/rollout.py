@@ -254,7 +254,9 @@ class PPO:
     """models/ppo/algo/ppo.py:6-104 over the device-resident RolloutStorage and ppo_loss.  actor_critic: the reference's
     Policy, or any module with is_recurrent, .base(obs, hxs, masks, infer=False) -> (value, actor_features, hxs, extra) and
     .dist holding .linear (Categorical) or .fc_mean and .logstd._bias (DiagGaussian).  Its forward and backward run in
-    PyTorch autograd; clip_grad_norm_ and optim.Adam as the reference."""
+    PyTorch autograd; clip_grad_norm_ and optim.Adam as the reference.  PPO(var_amd.bind_forward_gru(actor_critic), ...) puts
+    the recurrent sequence of that evaluation (NNBase._forward_gru) on var_amd.masked_gru: forward and backward in HIP, no
+    host read inside the update (gru_seq.py)."""
 
     def __init__(self, actor_critic, clip_param, ppo_epoch, num_mini_batch, value_loss_coef, entropy_coef, lr=None, eps=None,
                  max_grad_norm=None, use_clipped_value_loss=True, config=None):
