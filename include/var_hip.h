@@ -123,7 +123,9 @@ int var_arm_encoder_bwd(var_ctx* ctx, void* stream, const float* params,
 /* torch.nn.TripletMarginLoss(margin, p=2, eps=1e-6, reduction='mean')
  * (VAR/pretext_VAR.py:38,64) forward + backward in one launch.
  * loss_out[0] = sum_i hinge_i * inv_count;  g* = d(loss_out)/d(a|p|n).
- * inv_count = 1/B for the reference's mean; 1/B_global under data parallelism. */
+ * inv_count = 1/B for the reference's mean; 1/B_global under data parallelism.
+ * A row whose hinge argument d(a,p) - d(a,n) + margin is exactly 0 counts as inactive (zero gradients), like every
+ * negative one.  ga, gp, gn may each be NULL (not written). */
 int var_triplet_fwd_bwd(var_ctx* ctx, void* stream, const float* a, const float* p, const float* n,
                         int B, float margin, float inv_count,
                         float* loss_out, float* ga, float* gp, float* gn);

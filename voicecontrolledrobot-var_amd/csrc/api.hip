@@ -591,30 +591,39 @@ int var_adam_step(var_ctx* c, void* stream, float* params, const float* grads, f
     return VAR_OK;
 }
 
-int var_adam_step_dev(var_ctx* c, void* stream, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
-                      long n, const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
-                      int* step_dev) {
-    return var_adam_step_graph(c, stream, params, grads, exp_avg, exp_avg_sq, n, lr_dev, beta1, beta2, eps,
-                               weight_decay, step_dev, nullptr, 0, 0, nullptr, nullptr, 0);
-}
-
-int var_adam_step_graph(var_ctx* c, void* stream, float* params, const float* grads, float* exp_avg,
-                        float* exp_avg_sq, long n, const float* lr_dev, float beta1, float beta2, float eps,
-                        float weight_decay, int* step_dev, const int* index_table, int row_ints, int n_rows,
-                        int* cursor_dev, int* index_row, int ahead_from) {
+// the device-counter step behind both entries; `who` names the entry in the error text
+static int adam_step_dev_impl(var_ctx* c, void* stream, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                              long n, const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
+                              int* step_dev, const int* index_table, int row_ints, int n_rows, int* cursor_dev,
+                              int* index_row, int ahead_from, const char* who) {
     CHECK_CTX(c);
     if (!params || !grads || !exp_avg || !exp_avg_sq || !lr_dev || !step_dev || n <= 0) {
-        VAR_SET_ERR(c, "var_adam_step_dev: bad argument");
+        VAR_SET_ERR(c, "%s: bad argument", who);
         return VAR_ERR_ARG;
     }
     if (index_table && (!cursor_dev || !index_row || row_ints <= 0 || n_rows <= 0)) {
-        VAR_SET_ERR(c, "var_adam_step_graph: index table without cursor / row buffer / sizes");
+        VAR_SET_ERR(c, "%s: index table without cursor / row buffer / sizes", who);
         return VAR_ERR_ARG;
     }
     SET_DEVICE(c);
     return launch_adam_dev(c, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, n, lr_dev, beta1, beta2, eps,
                            weight_decay, step_dev, n == VAR_N_PARAMS && c->bound->params == params, index_table, row_ints, n_rows, cursor_dev, index_row,
                            ahead_from);
+}
+
+int var_adam_step_dev(var_ctx* c, void* stream, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                      long n, const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
+                      int* step_dev) {
+    return adam_step_dev_impl(c, stream, params, grads, exp_avg, exp_avg_sq, n, lr_dev, beta1, beta2, eps, weight_decay,
+                              step_dev, nullptr, 0, 0, nullptr, nullptr, 0, "var_adam_step_dev");
+}
+
+int var_adam_step_graph(var_ctx* c, void* stream, float* params, const float* grads, float* exp_avg,
+                        float* exp_avg_sq, long n, const float* lr_dev, float beta1, float beta2, float eps,
+                        float weight_decay, int* step_dev, const int* index_table, int row_ints, int n_rows,
+                        int* cursor_dev, int* index_row, int ahead_from) {
+    return adam_step_dev_impl(c, stream, params, grads, exp_avg, exp_avg_sq, n, lr_dev, beta1, beta2, eps, weight_decay,
+                              step_dev, index_table, row_ints, n_rows, cursor_dev, index_row, ahead_from, "var_adam_step_graph");
 }
 
 int var_mfcc(var_ctx* c, void* stream, const int16_t* pcm, const int* lens, const int* clip_index, int nclips,
