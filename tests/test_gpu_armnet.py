@@ -94,8 +94,8 @@ def test_sampling_and_rejections(var_amd, fx):
 
 @pytest.mark.parametrize("B", [1, 5, 8])
 def test_fused_small_batch_chain_equals_the_per_layer_path(var_amd, fx, B):
-    """B <= 8 (the RL stage's envs) takes the one-launch MLP chain after the convolutions (csrc/armnet.hip:
-    armnet_chain_kernel); larger batches take one launch per layer.  The same rows through both: a batch of B alone, and
+    """B <= 8 (the RL stage's envs) takes the one-launch MLP chain after the convolutions (csrc/chain.h:
+    mlp_chain_kernel); larger batches take one launch per layer.  The same rows through both: a batch of B alone, and
     as the first B rows of a batch of 12.  Two consecutive steps (the second from the first's hidden state)."""
     ref = armnet_seeded(int(fx["seed"]))
     m = make(var_amd, ref)
@@ -110,6 +110,10 @@ def test_fused_small_batch_chain_equals_the_per_layer_path(var_amd, fx, B):
     v2, a2, _, h2 = m.act(big, hxs, masks, deterministic=True)
     for got, want in ((v1, v2), (a1, a2), (h1, h2)):
         np.testing.assert_allclose(got.cpu().numpy(), want[:B].cpu().numpy(), rtol=0, atol=2e-5)
+    # get_value runs the same forward without the mean layer (a NULL head): the value's bits must not depend on it
+    np.testing.assert_allclose(m.get_value(small, hxs[:B].contiguous(), masks[:B].contiguous()).cpu().numpy(), v1.cpu().numpy(),
+                               rtol=0, atol=0)
+    np.testing.assert_allclose(m.get_value(big, hxs, masks).cpu().numpy(), v2.cpu().numpy(), rtol=0, atol=0)
     v3, a3, _, h3 = m.act(small, h1, torch.ones(B, 1, device="cuda"), deterministic=True)
     v4, a4, _, h4 = m.act(big, h2, torch.ones(12, 1, device="cuda"), deterministic=True)
     for got, want in ((v3, v4), (a3, a4), (h3, h4)):

@@ -144,6 +144,10 @@ def test_chain_equals_the_per_layer_path_and_cpu(var_amd, fx, B):
         close(got, want, 2e-5)
     for got, want in zip(o2, cpu_ref(m, obs, hxs, masks)):
         close(got, want, 2e-5)
+    # get_value runs the same forward without the logit layer (a NULL head): the value's bits must not depend on it
+    close(m.get_value(small, hxs[:B].contiguous(), masks[:B].contiguous()),
+          m.act(small, hxs[:B].contiguous(), masks[:B].contiguous(), deterministic=True)[0], 0)
+    close(m.get_value(obs, hxs, masks), m.act(obs, hxs, masks, deterministic=True)[0], 0)
     o3 = m._base_forward(small, o1[3], torch.ones(B, 1, device="cuda"))
     o4 = m._base_forward(obs, o2[3], torch.ones(12, 1, device="cuda"))
     for got, want in zip(o3, o4):

@@ -27,8 +27,9 @@ def _ortho(m, gain):
     return m
 
 
-class _Base(nn.Module):
-    """Parameter container with armNet_VAR's attribute names, construction order and initialisers."""
+class _TrunkBase(nn.Module):
+    """What armNet_VAR and ai2thorNet_VAR construct alike, in the reference's order: NNBase's GRU first (then the subclass's
+    convolutions), then _build_trunk's gain sqrt(2) orthogonal Linear layers."""
 
     def __init__(self, config, recurrent, rin, rh, action_hidden):
         super().__init__()
@@ -40,6 +41,28 @@ class _Base(nn.Module):
                 nn.init.constant_(p, 0)
             elif 'weight' in name:
                 nn.init.orthogonal_(p)
+
+    def _build_trunk(self, motor, im_hidden):
+        """motor: the widths of motorMlp; im_hidden: imgMotorMlp's hidden width."""
+        rin, rh, g = self.gru.input_size, self._recurrent_size, float(np.sqrt(2))
+        mlp = lambda *w: nn.Sequential(*(m for i, o in zip(w, w[1:]) for m in (_ortho(nn.Linear(i, o), g), nn.ReLU())))  # noqa: E731
+        self.motorMlp = mlp(*motor)
+        self.cnnMlp = mlp(1152, 512, 256)
+        self.imgMotorMlp = mlp(256, im_hidden, rin)
+        self.imgMotorMlp2 = mlp(rh, 256)
+        self.soundMlp = mlp(3, 128, 256, 256)
+        self.fusionMlp = mlp(256, 512, 256)
+        self.mlp_all = mlp(256, 256, 128)
+        self.actor = mlp(128, 128, self._action_hidden_size)
+        self.critic = mlp(128, 128, 128)
+        self.critic_linear = _ortho(nn.Linear(128, 1), g)
+
+
+class _Base(_TrunkBase):
+    """Parameter container with armNet_VAR's attribute names, construction order and initialisers."""
+
+    def __init__(self, config, recurrent, rin, rh, action_hidden):
+        super().__init__(config, recurrent, rin, rh, action_hidden)
         self.imgCNN = nn.Sequential(
             nn.Conv2d(3, 32, 3, stride=1, padding=1), nn.ReLU(), nn.Conv2d(32, 32, 3, stride=1, padding=1), nn.ReLU(),
             nn.MaxPool2d(2, stride=2),
@@ -51,20 +74,7 @@ class _Base(nn.Module):
             nn.Flatten())
         torch.rand((1, *config.img_dim))                      # the reference's shape probe draws here
         self.imgCNN_outputShape = torch.Size((1, 1152))
-        g = float(np.sqrt(2))
-        lin = lambda i, o: _ortho(nn.Linear(i, o), g)         # noqa: E731
-        self.motorMlp = nn.Sequential(lin(config.representationDim + config.robotStateDim, 256), nn.ReLU(),
-                                      lin(256, 512), nn.ReLU(), lin(512, 256), nn.ReLU())
-        self.cnnMlp = nn.Sequential(lin(1152, 512), nn.ReLU(), lin(512, 256), nn.ReLU())
-        self.imgMotorMlp = nn.Sequential(lin(256, 256), nn.ReLU(), lin(256, rin), nn.ReLU())
-        self.imgMotorMlp2 = nn.Sequential(lin(rh, 256), nn.ReLU())
-        self.soundMlp = nn.Sequential(lin(config.representationDim, 128), nn.ReLU(), lin(128, 256), nn.ReLU(),
-                                      lin(256, 256), nn.ReLU())
-        self.fusionMlp = nn.Sequential(lin(256, 512), nn.ReLU(), lin(512, 256), nn.ReLU())
-        self.mlp_all = nn.Sequential(lin(256, 256), nn.ReLU(), lin(256, 128), nn.ReLU())
-        self.actor = nn.Sequential(lin(128, 128), nn.ReLU(), lin(128, action_hidden), nn.ReLU())
-        self.critic = nn.Sequential(lin(128, 128), nn.ReLU(), lin(128, 128), nn.ReLU())
-        self.critic_linear = lin(128, 1)
+        self._build_trunk((config.representationDim + config.robotStateDim, 256, 512, 256), 256)
 
 
 class _AddBias(nn.Module):
@@ -109,14 +119,80 @@ class _ArenaPolicy(nn.Module):
     def forward(self, inputs, rnn_hxs, masks):
         raise NotImplementedError                             # as the reference (models/ppo/model.py:55-56)
 
+    # Per class: _C, the prefix of its C entry points; _INPUTS, observation name -> (shape after the batch dimension, whether it
+    # is an image that may stay uint8: divided by 255 on the device).  Per instance: _count_args, what var_*_param_count takes;
+    # _n_head, the width of the distribution's Linear layer.
+    def _finish_init(self, count_args, n_head):
+        self._count_args, self._n_head = count_args, n_head
+        self._flat = None
+        self._plan = 0
+        self._flatten_params()
+
+    def _call(self, c, name, *args):
+        fn = f"{self._C}_{name}"
+        c.check(getattr(c.lib, fn)(c.handle, *args), fn)
+
+    @property
+    def is_recurrent(self):
+        return True
+
     @staticmethod
-    def _prep(t, shape):
+    def _prep(t, shape, image=False):
         if not t.is_cuda:
             raise VarHipError("inputs must be CUDA tensors (no CPU fallback)")
+        if image:
+            return (t if t.dtype == torch.uint8 else t.float()).reshape(shape).contiguous()
         t = t.float().contiguous()
         if tuple(t.shape) != tuple(shape):
             raise VarHipError(f"expected shape {shape}, got {tuple(t.shape)}")
         return t
+
+    def _ensure_plan(self, c, B):
+        if self._flat.numel() != getattr(c.lib, self._C + "_param_count")(*self._count_args):
+            raise VarHipError(f"parameter arena does not match {self._C}_param_count()")
+        if self._plan < B:
+            self._call(c, "plan", int(B))
+            self._plan = B
+
+    def _base_forward(self, inputs, rnn_hxs, masks, head=True):
+        """(value, actor_features, action mean / logits or None without `head`, rnn_hxs_out) of one forward."""
+        if not self._arena_intact():
+            self._flatten_params()
+        flat = self._flat
+        if not flat.is_cuda:
+            raise VarHipError(f"{type(self).__name__} runs on the GPU only: call .to('cuda') (no CPU fallback)")
+        c = Context.get(flat.device.index)
+        B, H = inputs['image'].shape[0], self.recurrent_hidden_state_size
+        obs = {k: self._prep(inputs[k], (B, *tail), image) for k, (tail, image) in self._INPUTS.items()}
+        hxs, m = self._prep(rnn_hxs, (B, H)), self._prep(masks, (B, 1))
+        self._ensure_plan(c, B)
+        out = lambda n: torch.empty((B, n), dtype=torch.float32, device=flat.device)   # noqa: E731
+        value, feats, head_out, hout = out(1), out(128), out(self._n_head) if head else None, out(H)
+        self._launch_forward(c, obs, hxs, m, value, feats, head_out, hout)
+        return value, feats, head_out, hout
+
+    def capture(self, batch, deterministic=False, seed=0, image_dtype=torch.uint8):
+        """act() for a fixed number of envs as one replayed HIP graph with on-device sampling: see ActStep.  image_dtype:
+        what the image inputs ('image', iTHOR's 'occupancy') will be fed as (uint8, or float32 already divided by 255).
+        'image_feat' and 'goal_sound_feat' may be the device tensors IntrinsicReward.step returned: no host round trip."""
+        return ActStep(self, batch, deterministic, seed, image_dtype)
+
+    def chain_status(self):
+        """Status of the small-batch (B <= 8) MLP chain launch, a persistent kernel that needs its 128 workgroups resident at
+        once: 1 = the most recent forward timed out (its outputs are NaN), 0x40000001 = an earlier one did since the last
+        clear_chain_status(), 0 = never.  Blocking.  (The reference's Policy.act, models/ppo/model.py:57-69, cannot fail;
+        a caller that shares the GPU checks this after a NaN value or once per rollout.)"""
+        import ctypes
+        w = ctypes.c_uint(0)
+        self._call(Context.get(self._flat.device.index), "status", ctypes.byref(w))
+        return int(w.value)
+
+    def clear_chain_status(self):
+        self._call(Context.get(self._flat.device.index), "clear_status")
+
+    @torch.no_grad()
+    def get_value(self, inputs, rnn_hxs, masks):
+        return self._base_forward(inputs, rnn_hxs, masks, head=False)[0]
 
     def evaluate_actions(self, inputs, rnn_hxs, masks, action):
         raise NotImplementedError("the networks' evaluation forward and backward stay in PyTorch: load this state_dict into "
@@ -239,6 +315,10 @@ class ActStep:
 
 
 class ArmNetPolicy(_ArenaPolicy):
+    _C = "var_armnet"
+    _INPUTS = {'image': ((-1, 96, 96), True), 'image_feat': ((3,), False), 'robot_pose': ((2,), False),
+               'goal_sound_feat': ((3,), False)}
+
     def __init__(self, obs_shape, action_space, config=None, base='arm_VAR', base_kwargs=None):
         super().__init__()
         kw = dict(recurrent=False, recurrentInputSize=128, recurrentSize=128, actionHiddenSize=128)
@@ -253,52 +333,11 @@ class ArmNetPolicy(_ArenaPolicy):
                               "robotStateDim 2, recurrent 128 -> 512, actionHiddenSize 128, 2 actions")
         self.base = _Base(config, True, 128, 512, 128)
         self.dist = _DiagGaussian(128, n_act)
-        self._flat = None
-        self._plan = 0
-        self._flatten_params()
-
-    @property
-    def is_recurrent(self):
-        return True
+        self._finish_init((), n_act)
 
     @property
     def recurrent_hidden_state_size(self):
         return 512
-
-    def _base_forward(self, inputs, rnn_hxs, masks):
-        if not self._arena_intact():
-            self._flatten_params()
-        flat = self._flat
-        if not flat.is_cuda:
-            raise VarHipError("ArmNetPolicy runs on the GPU only: call .to('cuda') (no CPU fallback)")
-        c = Context.get(flat.device.index)
-        image = inputs['image']
-        B = image.shape[0]
-        self._ensure_plan(c, B)
-        f32 = lambda t, shape: self._prep(t, shape)           # noqa: E731
-        if not image.is_cuda:
-            raise VarHipError("inputs must be CUDA tensors (no CPU fallback)")
-        if image.dtype != torch.uint8:
-            image = image.float()
-        image = image.reshape(B, -1, 96, 96).contiguous()
-        feat, pose = f32(inputs['image_feat'], (B, 3)), f32(inputs['robot_pose'], (B, 2))
-        goal = f32(inputs['goal_sound_feat'], (B, 3))
-        hxs, m = f32(rnn_hxs, (B, 512)), f32(masks, (B, 1))
-        dev = flat.device
-        value = torch.empty((B, 1), dtype=torch.float32, device=dev)
-        feats = torch.empty((B, 128), dtype=torch.float32, device=dev)
-        mean = torch.empty((B, 2), dtype=torch.float32, device=dev)
-        hout = torch.empty((B, 512), dtype=torch.float32, device=dev)
-        self._launch_forward(c, {'image': image, 'image_feat': feat, 'robot_pose': pose, 'goal_sound_feat': goal}, hxs, m,
-                             value, feats, mean, hout)
-        return value, feats, mean, hout
-
-    def _ensure_plan(self, c, B):
-        if self._flat.numel() != c.lib.var_armnet_param_count():
-            raise VarHipError("parameter arena does not match var_armnet_param_count()")
-        if self._plan < B:
-            c.check(c.lib.var_armnet_plan(c.handle, int(B)), "var_armnet_plan")
-            self._plan = B
 
     def _launch_forward(self, c, obs, hxs, masks, value, feats, mean, hout):
         """The C call on prepared tensors (contiguous, on the arena's device)."""
@@ -314,26 +353,6 @@ class ArmNetPolicy(_ArenaPolicy):
         return 0, 2, 512, self.dist.logstd._bias, {'image': ((B, 3, 96, 96), image_dtype), 'image_feat': ((B, 3), f),
                                                    'robot_pose': ((B, 2), f), 'goal_sound_feat': ((B, 3), f)}
 
-    def capture(self, batch, deterministic=False, seed=0, image_dtype=torch.uint8):
-        """act() for a fixed number of envs as one replayed HIP graph with on-device sampling: see ActStep.  image_dtype:
-        what 'image' will be fed as (uint8, or float32 already divided by 255)."""
-        return ActStep(self, batch, deterministic, seed, image_dtype)
-
-    def chain_status(self):
-        """Status of the small-batch (B <= 8) MLP chain launch, a persistent kernel that needs its 128 workgroups resident at
-        once: 1 = the most recent forward timed out (its outputs are NaN), 0x40000001 = an earlier one did since the last
-        clear_chain_status(), 0 = never.  Blocking.  (The reference's Policy.act, models/ppo/model.py:57-69, cannot fail;
-        a caller that shares the GPU checks this after a NaN value or once per rollout.)"""
-        import ctypes
-        c = Context.get(self._flat.device.index)
-        w = ctypes.c_uint(0)
-        c.check(c.lib.var_armnet_status(c.handle, ctypes.byref(w)), "var_armnet_status")
-        return int(w.value)
-
-    def clear_chain_status(self):
-        c = Context.get(self._flat.device.index)
-        c.check(c.lib.var_armnet_clear_status(c.handle), "var_armnet_clear_status")
-
     def _normal(self, mean):
         std = self.dist.logstd._bias.t().view(1, -1).expand_as(mean).exp()
         return torch.distributions.Normal(mean, std)
@@ -346,26 +365,14 @@ class ArmNetPolicy(_ArenaPolicy):
         action = mean if deterministic else dist.sample()
         return value, action, dist.log_prob(action).sum(-1, keepdim=True), rnn_hxs
 
-    @torch.no_grad()
-    def get_value(self, inputs, rnn_hxs, masks):
-        return self._base_forward(inputs, rnn_hxs, masks)[0]
 
-
-class _IthorBase(nn.Module):
+class _IthorBase(_TrunkBase):
     """Parameter container with ai2thorNet_VAR's attribute names, construction order and initialisers
     (models/RL/ai2thor_RL_model.py:7-85): NNBase's GRU first, default-initialised convolutions and occupancy MLP, gain
     sqrt(2) orthogonal Linear layers.  No shape probe draws in this model."""
 
     def __init__(self, config, rin, rh, action_hidden):
-        super().__init__()
-        self.config = config
-        self._recurrent, self._recurrent_size, self._action_hidden_size = True, rh, action_hidden
-        self.gru = nn.GRU(rin, rh)
-        for name, p in self.gru.named_parameters():
-            if 'bias' in name:
-                nn.init.constant_(p, 0)
-            elif 'weight' in name:
-                nn.init.orthogonal_(p)
+        super().__init__(config, True, rin, rh, action_hidden)
         self.imgCNN = nn.Sequential(
             nn.Conv2d(3, 32, 3, stride=1, padding=1), nn.ReLU(), nn.Conv2d(32, 32, 3, stride=1, padding=1), nn.ReLU(),
             nn.MaxPool2d(2, stride=2),
@@ -377,18 +384,7 @@ class _IthorBase(nn.Module):
         self.occupancyCNNMLP = nn.Sequential(
             nn.Conv2d(1, 64, 3, stride=2, padding=1), nn.ReLU(), nn.Conv2d(64, 32, 3, stride=2, padding=1), nn.ReLU(),
             nn.Flatten(), nn.Linear(32 * 9, 128), nn.ReLU(), nn.Linear(128, 256), nn.ReLU())
-        g = float(np.sqrt(2))
-        lin = lambda i, o: _ortho(nn.Linear(i, o), g)         # noqa: E731
-        self.motorMlp = nn.Sequential(lin(3, 64), nn.ReLU(), lin(64, 256), nn.ReLU())
-        self.cnnMlp = nn.Sequential(lin(128 * 3 * 3, 512), nn.ReLU(), lin(512, 256), nn.ReLU())
-        self.imgMotorMlp = nn.Sequential(lin(256, 64), nn.ReLU(), lin(64, rin), nn.ReLU())
-        self.imgMotorMlp2 = nn.Sequential(lin(rh, 256), nn.ReLU())
-        self.soundMlp = nn.Sequential(lin(3, 128), nn.ReLU(), lin(128, 256), nn.ReLU(), lin(256, 256), nn.ReLU())
-        self.fusionMlp = nn.Sequential(lin(256, 512), nn.ReLU(), lin(512, 256), nn.ReLU())
-        self.mlp_all = nn.Sequential(lin(256, 256), nn.ReLU(), lin(256, 128), nn.ReLU())
-        self.actor = nn.Sequential(lin(128, 128), nn.ReLU(), lin(128, action_hidden), nn.ReLU())
-        self.critic = nn.Sequential(lin(128, 128), nn.ReLU(), lin(128, 128), nn.ReLU())
-        self.critic_linear = lin(128, 1)
+        self._build_trunk((3, 64, 256), 64)
 
 
 class _Categorical(nn.Module):
@@ -404,6 +400,9 @@ class IthorNetPolicy(_ArenaPolicy):
     divided as processAI2Thor leaves them; 'image_feat' (B,3), 'goal_sound_feat' (B,3)."""
 
     MAX_ACTIONS = 16
+    _C = "var_ithor_policy"
+    _INPUTS = {'image': ((3, 96, 96), True), 'occupancy': ((1, 9, 9), True), 'image_feat': ((3,), False),
+               'goal_sound_feat': ((3,), False)}
 
     def __init__(self, obs_shape, action_space, config=None, base='ai2thor_VAR', base_kwargs=None):
         super().__init__()
@@ -420,56 +419,11 @@ class IthorNetPolicy(_ArenaPolicy):
         self.n_actions = n_act
         self.base = _IthorBase(config, 128, 1024, 128)
         self.dist = _Categorical(128, n_act)
-        self._flat = None
-        self._plan = 0
-        self._flatten_params()
-
-    @property
-    def is_recurrent(self):
-        return True
+        self._finish_init((n_act,), n_act)
 
     @property
     def recurrent_hidden_state_size(self):
         return 1024
-
-    @staticmethod
-    def _prep_u8(t, shape):
-        if not t.is_cuda:
-            raise VarHipError("inputs must be CUDA tensors (no CPU fallback)")
-        if t.dtype != torch.uint8:
-            t = t.float()
-        t = t.reshape(shape).contiguous()
-        return t
-
-    def _base_forward(self, inputs, rnn_hxs, masks, logits=True):
-        if not self._arena_intact():
-            self._flatten_params()
-        flat = self._flat
-        if not flat.is_cuda:
-            raise VarHipError("IthorNetPolicy runs on the GPU only: call .to('cuda') (no CPU fallback)")
-        c = Context.get(flat.device.index)
-        image = inputs['image']
-        B = image.shape[0]
-        image = self._prep_u8(image, (B, 3, 96, 96))
-        occ = self._prep_u8(inputs['occupancy'], (B, 1, 9, 9))
-        self._ensure_plan(c, B)
-        feat, goal = self._prep(inputs['image_feat'], (B, 3)), self._prep(inputs['goal_sound_feat'], (B, 3))
-        hxs, m = self._prep(rnn_hxs, (B, 1024)), self._prep(masks, (B, 1))
-        dev = flat.device
-        value = torch.empty((B, 1), dtype=torch.float32, device=dev)
-        feats = torch.empty((B, 128), dtype=torch.float32, device=dev)
-        out_logits = torch.empty((B, self.n_actions), dtype=torch.float32, device=dev) if logits else None
-        hout = torch.empty((B, 1024), dtype=torch.float32, device=dev)
-        self._launch_forward(c, {'image': image, 'occupancy': occ, 'image_feat': feat, 'goal_sound_feat': goal}, hxs, m,
-                             value, feats, out_logits, hout)
-        return value, feats, out_logits, hout
-
-    def _ensure_plan(self, c, B):
-        if self._flat.numel() != c.lib.var_ithor_policy_param_count(self.n_actions):
-            raise VarHipError("parameter arena does not match var_ithor_policy_param_count()")
-        if self._plan < B:
-            c.check(c.lib.var_ithor_policy_plan(c.handle, int(B)), "var_ithor_policy_plan")
-            self._plan = B
 
     def _launch_forward(self, c, obs, hxs, masks, value, feats, logits, hout):
         """The C call on prepared tensors (contiguous, on the arena's device)."""
@@ -486,24 +440,6 @@ class IthorNetPolicy(_ArenaPolicy):
         return 1, self.n_actions, 1024, None, {'image': ((B, 3, 96, 96), image_dtype), 'occupancy': ((B, 1, 9, 9), image_dtype),
                                                'image_feat': ((B, 3), f), 'goal_sound_feat': ((B, 3), f)}
 
-    def capture(self, batch, deterministic=False, seed=0, image_dtype=torch.uint8):
-        """act() for a fixed number of envs as one replayed HIP graph with on-device sampling: see ActStep.  image_dtype:
-        what 'image' and 'occupancy' will be fed as (uint8, or float32 already divided by 255).  'image_feat' and
-        'goal_sound_feat' may be the device tensors IntrinsicReward.step returned: no host round trip."""
-        return ActStep(self, batch, deterministic, seed, image_dtype)
-
-    def chain_status(self):
-        """As ArmNetPolicy.chain_status, for this policy's small-batch (B <= 8) chain launch."""
-        import ctypes
-        c = Context.get(self._flat.device.index)
-        w = ctypes.c_uint(0)
-        c.check(c.lib.var_ithor_policy_status(c.handle, ctypes.byref(w)), "var_ithor_policy_status")
-        return int(w.value)
-
-    def clear_chain_status(self):
-        c = Context.get(self._flat.device.index)
-        c.check(c.lib.var_ithor_policy_clear_status(c.handle), "var_ithor_policy_clear_status")
-
     @torch.no_grad()
     def act(self, inputs, rnn_hxs, masks, deterministic=False):
         """models/ppo/model.py:57-69: (value, action (B,1) int64, action_log_probs (B,1), rnn_hxs)."""
@@ -512,10 +448,6 @@ class IthorNetPolicy(_ArenaPolicy):
         action = dist.probs.argmax(dim=-1, keepdim=True) if deterministic else dist.sample().unsqueeze(-1)
         logp = dist.log_prob(action.squeeze(-1)).view(action.size(0), -1).sum(-1).unsqueeze(-1)
         return value, action, logp, rnn_hxs
-
-    @torch.no_grad()
-    def get_value(self, inputs, rnn_hxs, masks):
-        return self._base_forward(inputs, rnn_hxs, masks, logits=False)[0]
 
 
 def Policy(obs_shape, action_space, config=None, base=None, base_kwargs=None):

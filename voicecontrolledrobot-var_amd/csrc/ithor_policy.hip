@@ -5,7 +5,9 @@
 // up to the sampling.  Inference only.  The same three regimes as armnet.hip: up to 64 images the image stack runs on the
 // LDS-band kernels of c3f.h (filters re-packed per call inside conv 1's launch), up to 8 rows the 22 Linear layers + GRU
 // step run as one persistent launch (chain.h), larger batches take the gather-GEMM of gg.h layer by layer with the
-// parameters in place in their state_dict() layouts.
+// parameters in place in their state_dict() layouts.  What this forward shares with armnet.hip -- the elementwise kernels, the
+// launch helpers, the workspace, the band configurations of the image stack (also ithor_reward.hip's), the per-layer path from
+// the GRU step on -- lives in actor_critic.h.
 #include <string.h>
 
 #include "gg.h"
@@ -15,19 +17,18 @@ PH_DECL();
 }
 #include "c3f.h"
 #include "chain.h"
+#include "actor_critic.h"
 
 namespace {
 constexpr int kCh[7] = {3, 32, 32, 64, 64, 128, 128};       // imgCNN channels, conv l: kCh[l - 1] -> kCh[l]
 constexpr int kSide[7] = {96, 96, 96, 48, 24, 12, 3};       // output side of conv l (before its pool)
 constexpr int kRepr = 3, kRin = 128, kRh = 1024, kAct = 128, kFlat = 1152, kOcc = 288, kMaxActions = 16;
 
-struct Lin { int w, b, in, out; };
-struct PolLayout {
-    int g_wih, g_whh, g_bih, g_bhh;
+struct PolLayout : Trunk {
     int cw[6], cb[6];          // imgCNN.{0,2,5,8,11,14}
     int ow[2], ob[2];          // occupancyCNNMLP.{0,2}
     Lin occ[2];                // occupancyCNNMLP.{5,7}
-    Lin motor[2], cnn[2], im[2], im2, snd[3], fus[2], all[2], actor[2], critic[2], clin, logit;
+    Lin motor[2], cnn[2], im[2], logit;
     int total;
 };
 
@@ -55,30 +56,14 @@ PolLayout make_layout(int n_actions) {
     return L;
 }
 
-// the image stack as band kernels (c3f.h), bands / channel groups chosen for 192-256 workgroups at 8 images
-using IpC2 = c3f::Cfg<32, 32, 96, 4, 2, 1, true>;        // 96 -> pool 48: 192 workgroups
-using IpC3 = c3f::Cfg<32, 64, 48, 6, 1, 1, true>;        // 48 -> pool 24: 256
-using IpC4 = c3f::Cfg<64, 64, 24, 4, 1, 1, true>;        // 24 -> pool 12: 192
-using IpC5 = c3f::Cfg<64, 128, 12, 4, 1, 1, true>;       // 12 -> pool 6: 192
-using IpC6 = c3f::SmallCfg<128, 128, 6, 2, 3, 1>;        // stride 2 pad 1, 6 -> 3: 64
-constexpr int kBandMaxB = 64;      // beyond this the gather-GEMM's big tiles win
-constexpr long kSlab = 8L << 20;   // floats of split-K scratch
 constexpr long kChainFloats = (long)kChainRows * 32768;
 
-struct pol_state {
+struct pol_state : Workspace {
     int n_actions = 0;
     PolLayout L;
-    int maxB = 0;
-    float* ws = nullptr;
     float *a[7] = {nullptr}, *p[5] = {nullptr};        // conv outputs 1..6 (a[2..5]: the gather-GEMM path only), pooled maps 1..4
     float* occf = nullptr;                             // (B, 288): the occupancy convolutions' flattened output
-    float *t0 = nullptr, *t1 = nullptr, *t2 = nullptr, *t3 = nullptr;     // (B, 512) scratch rows
-    float *flat_img = nullptr, *motor = nullptr, *occ = nullptr, *sound = nullptr, *fusion = nullptr, *h0 = nullptr;
-    float *h1 = nullptr, *gi = nullptr, *gh = nullptr, *slab = nullptr;   // h1: the new hidden state (B, 1024)
-    float* chain = nullptr;
-    unsigned* sync = nullptr;          // chain.h: [1] finished workgroups, [2] epoch of the last timed-out launch, [3] next epoch, [4] sticky
-    c3f::f32x4* wpk = nullptr;         // conv 2..6 filters in MFMA A-fragment order, re-packed per forward
-    c3f::PackDesc pack{};
+    float *occ = nullptr, *h1 = nullptr;               // the occupancy branch (B, 256), the new hidden state (B, 1024)
 };
 
 // occupancyCNNMLP's two convolutions (1 -> 64, 3x3 s2 p1, 9 -> 5; 64 -> 32, 3x3 s2 p1, 5 -> 3; ReLU each): 0.2 MFLOP per env,
@@ -137,80 +122,6 @@ __global__ void __launch_bounds__(kOccT) ip_occ_kernel(const void* __restrict__ 
         s += P[b1 + co0 + tid / 9];
         out[(long)b * kOcc + co0 * 9 + tid] = s > 0.f ? s : 0.f;
     }
-}
-
-static __global__ void ip_pool_kernel(const float* __restrict__ x, float* __restrict__ y, long n, int H, int HP) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int px = (int)(i % HP), py = (int)((i / HP) % HP);
-    const long plane = i / ((long)HP * HP);
-    const float* q = x + plane * H * H + (long)(2 * py) * H + 2 * px;
-    y[i] = fmaxf(fmaxf(q[0], q[1]), fmaxf(q[H], q[H + 1]));
-}
-static __global__ void ip_add_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = a[i] + b[i];
-}
-static __global__ void ip_mask_kernel(const float* __restrict__ h, const float* __restrict__ mask, float* __restrict__ out, int B, int H) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < B * H) out[i] = h[i] * mask[i / H];
-}
-// torch.nn.GRU cell (gate order r, z, n); gi / gh include their biases
-static __global__ void ip_gru_cell_kernel(const float* __restrict__ gi, const float* __restrict__ gh, const float* __restrict__ h,
-                                          float* __restrict__ out, float* __restrict__ out2, int B, int H) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B * H) return;
-    const int b = i / H, j = i - b * H;
-    const float* a = gi + (long)b * 3 * H;
-    const float* g = gh + (long)b * 3 * H;
-    const float r = 1.f / (1.f + expf(-(a[j] + g[j])));
-    const float z = 1.f / (1.f + expf(-(a[H + j] + g[H + j])));
-    const float n = tanhf(a[2 * H + j] + r * g[2 * H + j]);
-    const float v = (1.f - z) * n + z * h[i];
-    out[i] = v;
-    out2[i] = v;
-}
-
-inline dim3 g1(long n) { return dim3((unsigned)((n + 255) / 256)); }
-#define IP_CHECK(c) VAR_HIP_CHECK(c, hipGetLastError())
-#define RUN(x) do { int r_ = (x); if (r_ != VAR_OK) return r_; } while (0)
-
-template <class G, bool U8>
-int conv(var_ctx* c, hipStream_t s, pol_state* st, const ConvDims& d, const void* x, const float* w, const float* bias, float* y) {
-    ConvFwdP<G, U8, false> p{};
-    p.M = d.B * d.HO * d.WO; p.N = d.COUT; p.K = d.CIN * G::KHW;
-    const long out = (long)p.M * p.N;
-    p.nsplit = gg_small_split(((p.M + GG_MT - 1) / GG_MT) * ((p.N + 63) / 64), p.K, out, kSlab);
-    p.d = d; p.x = x; p.w = w; p.bias = bias; p.y = y; p.slab = st->slab; p.sstride = out;
-    RUN(gg_launch(c, s, p));
-    if (p.nsplit > 1) {
-        hipLaunchKernelGGL(gg_finish_kernel, g1(out), dim3(256), 0, s, y, st->slab, out, p.nsplit, out, bias, d.COUT, d.HO * d.WO, 1);
-        IP_CHECK(c);
-    }
-    return VAR_OK;
-}
-int linear(var_ctx* c, hipStream_t s, pol_state* st, const float* P, const Lin& l, const float* X, float* Y, int rows, int relu) {
-    const long out = (long)rows * l.out;
-    const int ns = gg_small_split(((l.out + GG_MT - 1) / GG_MT) * ((rows + 63) / 64), l.in, out, kSlab);
-    if (ns > 1) {
-        DenseP<true, true, 2> p{};
-        p.M = l.out; p.N = rows; p.K = l.in; p.nsplit = ns;
-        p.A = P + l.w; p.sam = l.in; p.sak = 1; p.Bm = X; p.sbk = 1; p.sbn = l.in; p.C = st->slab; p.scm = 1; p.scn = l.out; p.sC = out;
-        RUN(gg_launch(c, s, p));
-        hipLaunchKernelGGL(gg_finish_kernel, g1(out), dim3(256), 0, s, Y, st->slab, out, ns, out, P + l.b, l.out, 1, relu);
-        IP_CHECK(c);
-        return VAR_OK;
-    }
-    DenseP<true, true, 0> p{};
-    p.M = l.out; p.N = rows; p.K = l.in; p.nsplit = 1;
-    p.A = P + l.w; p.sam = l.in; p.sak = 1; p.Bm = X; p.sbk = 1; p.sbn = l.in; p.C = Y; p.scm = 1; p.scn = l.out;
-    p.bias = P + l.b; p.relu = relu;
-    return gg_launch(c, s, p);
-}
-int add(var_ctx* c, hipStream_t s, const float* a, const float* b, float* out, int n) {
-    hipLaunchKernelGGL(ip_add_kernel, g1(n), dim3(256), 0, s, a, b, out, n);
-    IP_CHECK(c);
-    return VAR_OK;
 }
 
 // Everything after the convolutions for B <= 8 rows as ONE persistent launch (chain.h).  Stages (jobs of one stage run side
@@ -276,60 +187,9 @@ int chain_forward(var_ctx* c, hipStream_t s, pol_state* st, const float* P, cons
     return chain_launch(c, s, D, cb.lds_max, kChainG);
 }
 
-// B > 8 rows: one launch per Linear layer (+ the sums, the mask and the GRU cell)
-int layer_forward(var_ctx* c, hipStream_t s, pol_state* st, const float* P, const float* image_feat, const float* goal,
-                  const float* hxs, const float* masks, int B, float* value, float* actor_features, float* logits, float* hxs_out) {
-    const PolLayout& L = st->L;
-    // image_flatten = cnnMlp(flatten), motor = motorMlp(image_feat), occupancy = the occupancy Linear layers
-    RUN(linear(c, s, st, P, L.cnn[0], st->a[6], st->t0, B, 1));
-    RUN(linear(c, s, st, P, L.cnn[1], st->t0, st->flat_img, B, 1));
-    RUN(linear(c, s, st, P, L.motor[0], image_feat, st->t0, B, 1));
-    RUN(linear(c, s, st, P, L.motor[1], st->t0, st->motor, B, 1));
-    RUN(linear(c, s, st, P, L.occ[0], st->occf, st->t0, B, 1));
-    RUN(linear(c, s, st, P, L.occ[1], st->t0, st->occ, B, 1));
-    // imageMotor = imgMotorMlp(image_flatten + motor + occupancy)
-    RUN(add(c, s, st->flat_img, st->motor, st->t0, B * 256));
-    RUN(add(c, s, st->t0, st->occ, st->t1, B * 256));
-    RUN(linear(c, s, st, P, L.im[0], st->t1, st->t0, B, 1));
-    RUN(linear(c, s, st, P, L.im[1], st->t0, st->t2, B, 1));                       // (B,128)
-    // one GRU step from hxs * masks (models/ppo/model.py:118-121)
-    hipLaunchKernelGGL(ip_mask_kernel, g1((long)B * kRh), dim3(256), 0, s, hxs, masks, st->h0, B, kRh);
-    IP_CHECK(c);
-    {
-        const Lin ih{L.g_wih, L.g_bih, kRin, 3 * kRh}, hh{L.g_whh, L.g_bhh, kRh, 3 * kRh};
-        RUN(linear(c, s, st, P, ih, st->t2, st->gi, B, 0));
-        RUN(linear(c, s, st, P, hh, st->h0, st->gh, B, 0));
-        hipLaunchKernelGGL(ip_gru_cell_kernel, g1((long)B * kRh), dim3(256), 0, s, st->gi, st->gh, st->h0, st->h1, hxs_out, B, kRh);
-        IP_CHECK(c);
-    }
-    RUN(linear(c, s, st, P, L.im2, st->h1, st->t0, B, 1));                         // imageMotorRnn (B,256)
-    // sound, fusion
-    RUN(linear(c, s, st, P, L.snd[0], goal, st->t1, B, 1));
-    RUN(linear(c, s, st, P, L.snd[1], st->t1, st->t2, B, 1));
-    RUN(linear(c, s, st, P, L.snd[2], st->t2, st->sound, B, 1));
-    RUN(add(c, s, st->sound, st->flat_img, st->t1, B * 256));
-    RUN(linear(c, s, st, P, L.fus[0], st->t1, st->t2, B, 1));
-    RUN(linear(c, s, st, P, L.fus[1], st->t2, st->fusion, B, 1));
-    RUN(add(c, s, st->fusion, st->t0, st->t1, B * 256));
-    RUN(linear(c, s, st, P, L.all[0], st->t1, st->t2, B, 1));
-    RUN(linear(c, s, st, P, L.all[1], st->t2, st->t3, B, 1));                      // x (B,128)
-    RUN(linear(c, s, st, P, L.critic[0], st->t3, st->t0, B, 1));
-    RUN(linear(c, s, st, P, L.critic[1], st->t0, st->t1, B, 1));
-    RUN(linear(c, s, st, P, L.clin, st->t1, value, B, 0));
-    RUN(linear(c, s, st, P, L.actor[0], st->t3, st->t0, B, 1));
-    RUN(linear(c, s, st, P, L.actor[1], st->t0, actor_features, B, 1));
-    if (logits) RUN(linear(c, s, st, P, L.logit, actor_features, logits, B, 0));
-    return VAR_OK;
-}
 }  // namespace
 
-void ithor_policy_free(var_ctx* c) {
-    pol_state* st = (pol_state*)c->ipol;
-    if (!st) return;
-    if (st->ws) (void)hipFree(st->ws);
-    delete st;
-    c->ipol = nullptr;
-}
+void ithor_policy_free(var_ctx* c) { (void)ws_drop<pol_state>(c, &c->ipol, false); }
 
 extern "C" {
 
@@ -342,58 +202,19 @@ int var_ithor_policy_plan(var_ctx* c, int max_batch) {
     if (!c) return VAR_ERR_ARG;
     if (max_batch < 1 || max_batch > 4096) { VAR_SET_ERR(c, "var_ithor_policy_plan: batch %d outside 1..4096", max_batch); return VAR_ERR_ARG; }
     VAR_HIP_CHECK(c, hipSetDevice(c->device));
-    pol_state* st = (pol_state*)c->ipol;
-    if (st && st->maxB >= max_batch) return VAR_OK;
-    if (st) {      // retire (do not free) the superseded workspace: a captured act() graph may still replay on it
-        if (st->ws) { int rc = retire_block(c, st->ws); if (rc != VAR_OK) return rc; }
-        delete st;
-        c->ipol = nullptr;
-    }
-    st = new pol_state();
+    if (c->ipol && ((pol_state*)c->ipol)->maxB >= max_batch) return VAR_OK;
+    RUN(ws_drop<pol_state>(c, &c->ipol, true));
+    pol_state* st = new pol_state();
     c->ipol = st;
     st->maxB = max_batch;
-    const long B = max_batch;
-    long total = 0;
-    auto take = [&](long n) { long o = total; total += (n + 63) & ~63L; return o; };
-    long oa[7], op[5];
-    for (int l = 1; l <= 6; ++l) oa[l] = take(B * kCh[l] * kSide[l] * kSide[l]);
-    op[1] = take(B * 32 * 48 * 48); op[2] = take(B * 64 * 24 * 24); op[3] = take(B * 64 * 12 * 12); op[4] = take(B * 128 * 6 * 6);
-    const long oocf = take(B * kOcc);
-    const long ot0 = take(B * 512), ot1 = take(B * 512), ot2 = take(B * 512), ot3 = take(B * 512);
-    const long ofl = take(B * 256), omo = take(B * 256), ooc = take(B * 256), osn = take(B * 256), ofu = take(B * 256), oh0 = take(B * kRh), oh1 = take(B * kRh);
-    const long ogi = take(B * 3 * kRh), ogh = take(B * 3 * kRh), oslab = take(kSlab);
-    const long ochain = take(kChainFloats), osync = take(64);
-    {
-        const PolLayout L = make_layout(1);           // (the convolutions sit before the action-sized layer)
-        c3f::PackDesc& d = st->pack;
-        d.n_layers = 5;
-        int f4 = 0;
-        for (int i = 0; i < 5; ++i) {
-            const int l = i + 1;                      // imgCNN conv l+1: kCh[l] -> kCh[l + 1]
-            d.w_off[i] = L.cw[l]; d.cin[i] = kCh[l]; d.cout[i] = kCh[l + 1];
-            d.wp_off[i] = f4; d.first[i] = f4;
-            f4 += kCh[l] * kCh[l + 1] * 9 / 4;
-        }
-        d.first[5] = f4;
-    }
-    const long owpk = take(4L * st->pack.first[5]);
-    VAR_HIP_CHECK(c, hipMalloc((void**)&st->ws, (size_t)total * sizeof(float)));
-    float* w = st->ws;
-    for (int l = 1; l <= 6; ++l) st->a[l] = w + oa[l];
-    for (int l = 1; l <= 4; ++l) st->p[l] = w + op[l];
-    st->occf = w + oocf;
-    st->t0 = w + ot0; st->t1 = w + ot1; st->t2 = w + ot2; st->t3 = w + ot3;
-    st->flat_img = w + ofl; st->motor = w + omo; st->occ = w + ooc; st->sound = w + osn; st->fusion = w + ofu; st->h0 = w + oh0; st->h1 = w + oh1;
-    st->gi = w + ogi; st->gh = w + ogh; st->slab = w + oslab;
-    st->chain = w + ochain; st->sync = (unsigned*)(w + osync);
-    st->wpk = (c3f::f32x4*)(w + owpk);
-    VAR_HIP_CHECK(c, hipMemset(st->chain, 0, (size_t)kChainFloats * sizeof(float)));       // no tag of any launch yet
-    {
-        const unsigned init[4] = {0u, 0u, 0u, 1u};                  // [3]: the first launch's epoch
-        VAR_HIP_CHECK(c, hipMemset(st->sync, 0, 64 * sizeof(float)));
-        VAR_HIP_CHECK(c, hipMemcpy(st->sync, init, sizeof(init), hipMemcpyHostToDevice));
-    }
-    return VAR_OK;
+    st->pack = make_pack_desc(kCh + 1, make_layout(1).cw + 1, 5);      // conv 2..6 (they sit before the action-sized layer)
+    return ws_alloc(c, st, [st](Take& t) {
+        const long B = st->maxB;
+        for (int l = 1; l <= 6; ++l) st->a[l] = t(B * kCh[l] * kSide[l] * kSide[l]);
+        st->p[1] = t(B * 32 * 48 * 48); st->p[2] = t(B * 64 * 24 * 24); st->p[3] = t(B * 64 * 12 * 12); st->p[4] = t(B * 128 * 6 * 6);
+        st->occf = t(B * kOcc); st->occ = t(B * 256); st->h1 = t(B * kRh);
+        st->take_shared(t, kRh, kChainFloats);
+    });
 }
 
 int var_ithor_policy_forward(var_ctx* c, void* stream, const float* params, int n_actions, const void* image, int image_is_u8,
@@ -404,92 +225,69 @@ int var_ithor_policy_forward(var_ctx* c, void* stream, const float* params, int 
     VAR_HIP_CHECK(c, hipSetDevice(c->device));
     pol_state* st = (pol_state*)c->ipol;
     if (!st || B > st->maxB) { VAR_SET_ERR(c, "var_ithor_policy_forward: var_ithor_policy_plan(%d) first", B); return VAR_ERR_PLAN; }
-    if (!params || !image || !occupancy || !image_feat || !goal_sound_feat || !rnn_hxs || !masks || !value || !actor_features ||
-        !rnn_hxs_out || B < 1) {
-        VAR_SET_ERR(c, "var_ithor_policy_forward: NULL argument or B < 1");
-        return VAR_ERR_ARG;
-    }
+    RUN(check_forward_args(c, "var_ithor_policy_forward", params && image && occupancy && image_feat && goal_sound_feat && rnn_hxs && masks &&
+                           value && actor_features && rnn_hxs_out, B, image_bstride, rnn_hxs, rnn_hxs_out, kRh));
     if (n_actions < 1 || n_actions > kMaxActions) {
         VAR_SET_ERR(c, "var_ithor_policy_forward: n_actions %d outside 1..%d", n_actions, kMaxActions);
         return VAR_ERR_ARG;
-    }
-    if (image_bstride < 3L * 96 * 96) {
-        VAR_SET_ERR(c, "var_ithor_policy_forward: image stride %ld < 3*96*96", image_bstride);
-        return VAR_ERR_ARG;
-    }
-    {   // the small-batch chain reads rnn_hxs from every workgroup of its GRU stage while one of them writes rnn_hxs_out
-        const char *a0 = (const char*)rnn_hxs, *b0 = (const char*)rnn_hxs_out;
-        const size_t n = (size_t)B * kRh * sizeof(float);
-        if (a0 < b0 + n && b0 < a0 + n) {
-            VAR_SET_ERR(c, "var_ithor_policy_forward: rnn_hxs_out overlaps rnn_hxs (an in-place state update is not supported)");
-            return VAR_ERR_ARG;
-        }
     }
     if (st->n_actions != n_actions) { st->L = make_layout(n_actions); st->n_actions = n_actions; }
     hipStream_t s = (hipStream_t)stream;
     const PolLayout& L = st->L;
     const float* P = params;
+    float* slab = st->slab;
     // occupancyCNNMLP's convolutions (any batch)
     if (occupancy_is_u8) hipLaunchKernelGGL(ip_occ_kernel<true>, dim3(B * (32 / kOccCo)), dim3(kOccT), 0, s, occupancy, P, L.ow[0], L.ob[0], L.ow[1], L.ob[1], st->occf);
     else hipLaunchKernelGGL(ip_occ_kernel<false>, dim3(B * (32 / kOccCo)), dim3(kOccT), 0, s, occupancy, P, L.ow[0], L.ob[0], L.ow[1], L.ob[1], st->occf);
-    IP_CHECK(c);
+    AC_CHECK(c);
     // imgCNN
-    if (B <= kBandMaxB) {
+    if (B <= kBandMaxB) {      // conv 1 and the filter pack of conv 2..6 in one launch (c3f.h)
         const c3f::PackDesc& d = st->pack;
-        const int nconv = B * c3f::C1_BANDS, npack = (d.first[5] + 255) / 256;      // conv 1 and the filter pack of conv 2..6: one launch
-        if (image_is_u8) hipLaunchKernelGGL(c3f::c1f_pack_kernel<true>, dim3(nconv + npack), dim3(256), 0, s, image, image_bstride, P, L.cw[0],
-                                            L.cb[0], st->a[1], nconv, st->wpk, d);
-        else hipLaunchKernelGGL(c3f::c1f_pack_kernel<false>, dim3(nconv + npack), dim3(256), 0, s, image, image_bstride, P, L.cw[0], L.cb[0],
-                                st->a[1], nconv, st->wpk, d);
-        IP_CHECK(c);
-        RUN(c3f::launch<IpC2>(c, s, st->a[1], st->wpk + d.wp_off[0], P + L.cb[1], st->p[1], B));
-        RUN(c3f::launch<IpC3>(c, s, st->p[1], st->wpk + d.wp_off[1], P + L.cb[2], st->p[2], B));
-        RUN(c3f::launch<IpC4>(c, s, st->p[2], st->wpk + d.wp_off[2], P + L.cb[3], st->p[3], B));
-        RUN(c3f::launch<IpC5>(c, s, st->p[3], st->wpk + d.wp_off[3], P + L.cb[4], st->p[4], B));
-        RUN(c3f::launch_small<IpC6>(c, s, st->p[4], st->wpk + d.wp_off[4], P + L.cb[5], st->a[6], B));
+        RUN(conv1(c, s, image, image_is_u8, image_bstride, P, L.cw[0], L.cb[0], st->a[1], B, st->wpk, d));
+        RUN(c3f::launch<IthorC2>(c, s, st->a[1], st->wpk + d.wp_off[0], P + L.cb[1], st->p[1], B));
+        RUN(c3f::launch<IthorC3>(c, s, st->p[1], st->wpk + d.wp_off[1], P + L.cb[2], st->p[2], B));
+        RUN(c3f::launch<IthorC4>(c, s, st->p[2], st->wpk + d.wp_off[2], P + L.cb[3], st->p[3], B));
+        RUN(c3f::launch<IthorC5>(c, s, st->p[3], st->wpk + d.wp_off[3], P + L.cb[4], st->p[4], B));
+        RUN(c3f::launch_small<IthorC6>(c, s, st->p[4], st->wpk + d.wp_off[4], P + L.cb[5], st->a[6], B));
     } else {
         using S1 = Geo<3, 3, 1, 1, 1, 1>;
         using S2P1 = Geo<3, 3, 2, 2, 1, 1>;
         auto dims = [&](int l, int hin, int stride) { return conv_dims(B, kCh[l - 1], hin, hin, kCh[l], 3, 3, stride, stride, 1, 1); };
-        auto pool = [&](const float* x, float* y, int ch, int hin) -> int {
-            const long n = (long)B * ch * (hin / 2) * (hin / 2);
-            hipLaunchKernelGGL(ip_pool_kernel, g1(n), dim3(256), 0, s, x, y, n, hin, hin / 2);
-            IP_CHECK(c);
-            return VAR_OK;
-        };
         ConvDims d1 = dims(1, 96, 1);
         d1.xb = image_bstride;
-        if (image_is_u8) RUN((conv<S1, true>(c, s, st, d1, image, P + L.cw[0], P + L.cb[0], st->a[1])));
-        else RUN((conv<S1, false>(c, s, st, d1, image, P + L.cw[0], P + L.cb[0], st->a[1])));
-        RUN((conv<S1, false>(c, s, st, dims(2, 96, 1), st->a[1], P + L.cw[1], P + L.cb[1], st->a[2])));
-        RUN(pool(st->a[2], st->p[1], 32, 96));
-        RUN((conv<S1, false>(c, s, st, dims(3, 48, 1), st->p[1], P + L.cw[2], P + L.cb[2], st->a[3])));
-        RUN(pool(st->a[3], st->p[2], 64, 48));
-        RUN((conv<S1, false>(c, s, st, dims(4, 24, 1), st->p[2], P + L.cw[3], P + L.cb[3], st->a[4])));
-        RUN(pool(st->a[4], st->p[3], 64, 24));
-        RUN((conv<S1, false>(c, s, st, dims(5, 12, 1), st->p[3], P + L.cw[4], P + L.cb[4], st->a[5])));
-        RUN(pool(st->a[5], st->p[4], 128, 12));
-        RUN((conv<S2P1, false>(c, s, st, dims(6, 6, 2), st->p[4], P + L.cw[5], P + L.cb[5], st->a[6])));
+        if (image_is_u8) RUN((conv<S1, true>(c, s, slab, d1, image, P + L.cw[0], P + L.cb[0], st->a[1])));
+        else RUN((conv<S1, false>(c, s, slab, d1, image, P + L.cw[0], P + L.cb[0], st->a[1])));
+        RUN((conv<S1, false>(c, s, slab, dims(2, 96, 1), st->a[1], P + L.cw[1], P + L.cb[1], st->a[2])));
+        RUN(pool(c, s, st->a[2], st->p[1], B, 32, 96));
+        RUN((conv<S1, false>(c, s, slab, dims(3, 48, 1), st->p[1], P + L.cw[2], P + L.cb[2], st->a[3])));
+        RUN(pool(c, s, st->a[3], st->p[2], B, 64, 48));
+        RUN((conv<S1, false>(c, s, slab, dims(4, 24, 1), st->p[2], P + L.cw[3], P + L.cb[3], st->a[4])));
+        RUN(pool(c, s, st->a[4], st->p[3], B, 64, 24));
+        RUN((conv<S1, false>(c, s, slab, dims(5, 12, 1), st->p[3], P + L.cw[4], P + L.cb[4], st->a[5])));
+        RUN(pool(c, s, st->a[5], st->p[4], B, 128, 12));
+        RUN((conv<S2P1, false>(c, s, slab, dims(6, 6, 2), st->p[4], P + L.cw[5], P + L.cb[5], st->a[6])));
     }
     if (B <= kChainRows)      // the RL stage's batch: everything after the convolutions in one persistent launch
         return chain_forward(c, s, st, P, image_feat, goal_sound_feat, rnn_hxs, masks, B, value, actor_features, logits, rnn_hxs_out);
-    return layer_forward(c, s, st, P, image_feat, goal_sound_feat, rnn_hxs, masks, B, value, actor_features, logits, rnn_hxs_out);
+    // B > 8 rows: one launch per Linear layer (+ the sums, the mask and the GRU cell)
+    // image_flatten = cnnMlp(flatten), motor = motorMlp(image_feat), occupancy = the occupancy Linear layers
+    RUN(linear(c, s, slab, P, L.cnn[0], st->a[6], st->t0, B, 1));
+    RUN(linear(c, s, slab, P, L.cnn[1], st->t0, st->flat_img, B, 1));
+    RUN(linear(c, s, slab, P, L.motor[0], image_feat, st->t0, B, 1));
+    RUN(linear(c, s, slab, P, L.motor[1], st->t0, st->motor, B, 1));
+    RUN(linear(c, s, slab, P, L.occ[0], st->occf, st->t0, B, 1));
+    RUN(linear(c, s, slab, P, L.occ[1], st->t0, st->occ, B, 1));
+    // imageMotor = imgMotorMlp(image_flatten + motor + occupancy)
+    RUN(add(c, s, st->flat_img, st->motor, st->t0, B * 256));
+    RUN(add(c, s, st->t0, st->occ, st->t1, B * 256));
+    RUN(linear(c, s, slab, P, L.im[0], st->t1, st->t0, B, 1));
+    RUN(linear(c, s, slab, P, L.im[1], st->t0, st->t2, B, 1));                       // (B,128)
+    return layer_tail(c, s, st, P, L, L.logit, kRin, kRh, st->t2, st->h1, goal_sound_feat, rnn_hxs, masks, B, value, actor_features, logits,
+                      rnn_hxs_out);
 }
 
-int var_ithor_policy_status(var_ctx* c, unsigned* word) {
-    if (!c) return VAR_ERR_ARG;
-    pol_state* st = (pol_state*)c->ipol;
-    if (!st || !word) { VAR_SET_ERR(c, "var_ithor_policy_status: var_ithor_policy_plan first"); return VAR_ERR_PLAN; }
-    VAR_HIP_CHECK(c, hipSetDevice(c->device));
-    return chain_status_word(c, st->sync, word);
-}
+int var_ithor_policy_status(var_ctx* c, unsigned* word) { return chain_status(c, c ? (pol_state*)c->ipol : nullptr, word, "var_ithor_policy"); }
 
-int var_ithor_policy_clear_status(var_ctx* c) {
-    if (!c) return VAR_ERR_ARG;
-    pol_state* st = (pol_state*)c->ipol;
-    if (!st) { VAR_SET_ERR(c, "var_ithor_policy_clear_status: var_ithor_policy_plan first"); return VAR_ERR_PLAN; }
-    VAR_HIP_CHECK(c, hipSetDevice(c->device));
-    return chain_clear_status(c, st->sync);
-}
+int var_ithor_policy_clear_status(var_ctx* c) { return chain_clear(c, c ? (pol_state*)c->ipol : nullptr, "var_ithor_policy"); }
 
 }  // extern "C"

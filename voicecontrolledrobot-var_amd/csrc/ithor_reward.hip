@@ -12,7 +12,8 @@
 // The encoder is frozen: var_ithor_reward_pack copies the parameter arena into the plan's own memory and lays conv 2..6 out in
 // MFMA A-fragment order ONCE; every step reads that snapshot, so parameters loaded later change nothing until the next pack.
 // The plan owns every buffer it touches (nothing of var_ithor_plan / var_ithor_policy_plan / var_plan is borrowed), and no
-// kernel here waits for another workgroup.
+// kernel here waits for another workgroup.  The band configurations of the image stack, the filter-pack descriptor and the
+// conv 1 launch are the iTHOR policy's: image_stack.h.
 #include <string.h>
 
 #include "gg.h"
@@ -21,13 +22,13 @@ namespace {
 PH_DECL();
 }
 #include "c3f.h"
+#include "image_stack.h"
 
 namespace {
 constexpr int kCh[7] = {3, 32, 32, 64, 64, 128, 128};
 constexpr int kT = 600, kF = 40;                       // sound_dim (1,600,40)
 constexpr int kSeq = 73, kGin = 448, kGh = 512, kG3 = 1536;
 constexpr int kIRaw = 1152, kSRaw = 1024, kHidI = 128;
-constexpr int kBandMaxB = 64;                          // the band kernels' limit (armnet.hip, ithor_policy.hip)
 constexpr int kFusedClips = 16;                        // one MFMA column block of rw_gru_step_kernel
 constexpr int kRecSplit = 4;                           // K splits of the two-launch recurrent product (ithor.hip: rec_split at <= 64 clips)
 
@@ -57,13 +58,6 @@ RewLayout make_layout() {
     L.total = o;
     return L;
 }
-
-// the image stack as band kernels: the iTHOR policy's choices (ithor_policy.hip: 192-256 workgroups at 8 images)
-using RwC2 = c3f::Cfg<32, 32, 96, 4, 2, 1, true>;        // 96 -> pool 48
-using RwC3 = c3f::Cfg<32, 64, 48, 6, 1, 1, true>;        // 48 -> pool 24
-using RwC4 = c3f::Cfg<64, 64, 24, 4, 1, 1, true>;        // 24 -> pool 12
-using RwC5 = c3f::Cfg<64, 128, 12, 4, 1, 1, true>;       // 12 -> pool 6
-using RwC6 = c3f::SmallCfg<128, 128, 6, 2, 3, 1>;        // stride 2 pad 1, 6 -> 3
 
 using GS1 = Geo<11, 11, 2, 2, 5, 5>;
 using GS2 = Geo<11, 5, 2, 2, 5, 5>;
@@ -261,9 +255,6 @@ __global__ void rw_gru_gate_kernel(const float* __restrict__ GI, const float* __
     hnext[(long)clip * kSRaw + dir * kGh + j] = (1.f - z) * n + z * hp;
 }
 
-#define RW_CHECK(c) VAR_HIP_CHECK(c, hipGetLastError())
-#define RUN(x) do { int r_ = (x); if (r_ != VAR_OK) return r_; } while (0)
-
 // the fp32 gather-GEMM, whatever var_ithor_set_bf16 says
 template <class G, bool SEQ>
 int snd_conv(var_ctx* c, hipStream_t s, const ConvDims& d, const float* x, const float* w, const float* bias, float* y) {
@@ -305,7 +296,7 @@ int goal_branch(var_ctx* c, hipStream_t s, rew_state* st, const float* goal, int
         if (B <= kFusedClips) {
             hipLaunchKernelGGL(rw_gru_step_kernel, dim3(kGruWG), dim3(256), 0, s, P + L.w_hh[0], P + L.b_hh[0], dirP, st->GI, dirGI, hprev,
                                hnext, B, step, step == 0 ? 1 : 0);
-            RW_CHECK(c);
+            AC_CHECK(c);
             continue;
         }
         if (step > 0) {      // (h_0 = 0: no product)
@@ -318,7 +309,7 @@ int goal_branch(var_ctx* c, hipStream_t s, rew_state* st, const float* goal, int
         }
         hipLaunchKernelGGL(rw_gru_gate_kernel, dim3((B * kGh + 255) / 256, 2), dim3(256), 0, s, st->GI, st->GH, kRecSplit, hprev, hnext,
                            P + L.b_hh[0], dirP, B, step, dirGI, step == 0 ? 1 : 0);
-        RW_CHECK(c);
+        AC_CHECK(c);
     }
     const float* sraw = st->Hb + (kSeq & 1) * slot;
     RUN(linear(c, s, sraw, P + L.sh_w0, P + L.sh_b0, st->hs1, B, kSRaw, 128, 1));
@@ -365,18 +356,7 @@ int var_ithor_reward_plan(var_ctx* c, int max_batch, int img_hw) {
     c->irew = st;
     st->L = L;
     st->maxB = max_batch;
-    {
-        c3f::PackDesc& d = st->pack;
-        d.n_layers = 5;
-        int f4 = 0;
-        for (int i = 0; i < 5; ++i) {
-            const int l = i + 1;                      // conv l + 1: kCh[l] -> kCh[l + 1]
-            d.w_off[i] = st->L.iw[l]; d.cin[i] = kCh[l]; d.cout[i] = kCh[l + 1];
-            d.wp_off[i] = f4; d.first[i] = f4;
-            f4 += kCh[l] * kCh[l + 1] * 9 / 4;
-        }
-        d.first[5] = f4;
-    }
+    st->pack = make_pack_desc(kCh + 1, st->L.iw + 1, 5);          // conv 2..6
     const long B = max_batch;
     long total = 0;
     auto take = [&](long n) { long o = total; total += (n + 63) & ~63L; return o; };
@@ -408,7 +388,7 @@ int var_ithor_reward_pack(var_ctx* c, void* stream, const float* params) {
     hipStream_t s = (hipStream_t)stream;
     RUN(var_copy_async(c, s, st->frozen, params, sizeof(float) * (size_t)st->L.total));
     hipLaunchKernelGGL(rw_pack_kernel, dim3((st->pack.first[5] + 255) / 256), dim3(256), 0, s, (const float*)st->frozen, st->wpk, st->pack);
-    RW_CHECK(c);
+    AC_CHECK(c);
     st->packed = true;
     st->packed_from = params;
     return VAR_OK;
@@ -437,24 +417,17 @@ int var_ithor_reward_step(var_ctx* c, void* stream, const float* params, const v
     const RewLayout& L = st->L;
     const float* P = st->frozen;
     const c3f::PackDesc& d = st->pack;
-    {   // conv 1: c1f_pack_kernel's convolution workgroups alone (the filters were packed once)
-        const int nconv = B * c3f::C1_BANDS;
-        const c3f::PackDesc none{};
-        if (image_is_u8) hipLaunchKernelGGL(c3f::c1f_pack_kernel<true>, dim3(nconv), dim3(256), 0, s, image, image_bstride, P, L.iw[0], L.ib[0],
-                                            st->a1, nconv, (c3f::f32x4*)nullptr, none);
-        else hipLaunchKernelGGL(c3f::c1f_pack_kernel<false>, dim3(nconv), dim3(256), 0, s, image, image_bstride, P, L.iw[0], L.ib[0], st->a1,
-                                nconv, (c3f::f32x4*)nullptr, none);
-        RW_CHECK(c);
-    }
-    RUN(c3f::launch<RwC2>(c, s, st->a1, st->wpk + d.wp_off[0], P + L.ib[1], st->p[1], B));
-    RUN(c3f::launch<RwC3>(c, s, st->p[1], st->wpk + d.wp_off[1], P + L.ib[2], st->p[2], B));
-    RUN(c3f::launch<RwC4>(c, s, st->p[2], st->wpk + d.wp_off[2], P + L.ib[3], st->p[3], B));
-    RUN(c3f::launch<RwC5>(c, s, st->p[3], st->wpk + d.wp_off[3], P + L.ib[4], st->p[4], B));
-    RUN(c3f::launch_small<RwC6>(c, s, st->p[4], st->wpk + d.wp_off[4], P + L.ib[5], st->a6, B));
+    // conv 1: c1f_pack_kernel's convolution workgroups alone (the filters were packed once)
+    RUN(conv1(c, s, image, image_is_u8, image_bstride, P, L.iw[0], L.ib[0], st->a1, B, nullptr, c3f::PackDesc{}));
+    RUN(c3f::launch<IthorC2>(c, s, st->a1, st->wpk + d.wp_off[0], P + L.ib[1], st->p[1], B));
+    RUN(c3f::launch<IthorC3>(c, s, st->p[1], st->wpk + d.wp_off[1], P + L.ib[2], st->p[2], B));
+    RUN(c3f::launch<IthorC4>(c, s, st->p[2], st->wpk + d.wp_off[2], P + L.ib[3], st->p[3], B));
+    RUN(c3f::launch<IthorC5>(c, s, st->p[3], st->wpk + d.wp_off[3], P + L.ib[4], st->p[4], B));
+    RUN(c3f::launch_small<IthorC6>(c, s, st->p[4], st->wpk + d.wp_off[4], P + L.ib[5], st->a6, B));
     if (goal_mfcc) RUN(goal_branch(c, s, st, goal_mfcc, B));
     hipLaunchKernelGGL(rw_tail_kernel, dim3(kTailWG), dim3(256), 0, s, (const float*)st->a6, P + L.ih_w0, P + L.ih_b0, P + L.ih_w1, P + L.ih_b1,
                        B, st->hid, st->ctr, goal_mfcc ? (const float*)st->graw : (const float*)nullptr, goal_feat, image_feat, reward);
-    RW_CHECK(c);
+    AC_CHECK(c);
     return VAR_OK;
 }
 
