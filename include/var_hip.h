@@ -488,6 +488,52 @@ int var_gru_seq_bwd(var_ctx* ctx, void* stream, const float* x, const float* mas
                     float* d_x, float* d_hxs, float* d_w_ih, float* d_w_hh, float* d_b_ih, float* d_b_hh, void* workspace,
                     long workspace_bytes);
 
+/* The PPO update's MLP trunk, forward and backward -------------------------------------------------------------------------
+ * Everything between imgCNN's flattened output and the distribution head of armNet_VAR (kind 0, models/RL/arm_RL_model.py:
+ * 102-134) and ai2thorNet_VAR (kind 1, models/RL/ai2thor_RL_model.py:85-115), as PPO.update evaluates it on a minibatch of
+ * M = T*N rows ordered (t, n).  Inputs: feat (M, 1152), motor_in (M, 5 | 3: kind 0's is cat(image_feat, robot_pose)), sound_in
+ * (M, 3), occ (M, 288: occupancyCNNMLP's flattened convolution output, kind 1 only), hxs (N, H), masks (M, 1).  With every
+ * named layer a Linear + ReLU:
+ *     flat = cnnMlp(feat)   motor = motorMlp(motor_in)   sound = soundMlp(sound_in)   occv = occupancyCNNMLP[5..8](occ)
+ *     x = imgMotorMlp((flat + motor) [+ occv])           g, h_T = the masked GRU above (x, hxs, masks), unchanged
+ *     rnn = imgMotorMlp2(g)   fusion = fusionMlp(sound + flat)   y = mlp_all(fusion + rnn)
+ *     value = critic_linear(critic(y)) (no ReLU on critic_linear)   actor_features = actor(y)
+ * kind 0: H 512, motorMlp 5-256-512-256, imgMotorMlp 256-256-128 (20 layers); kind 1: H 1024, motorMlp 3-64-256, imgMotorMlp
+ * 256-64-128, the occupancy branch (21 layers).  T = 1 is the single-step branch.  fp32; the ReLU gradient is autograd's
+ * (zero where the output is zero).
+ *   var_trunk_n_params / _param_floats / _grad_offset   the published parameter order: the four GRU tensors (weight_ih_l0,
+ *       weight_hh_l0, bias_ih_l0, bias_hh_l0), then weight and bias of every trunk layer in the base's state_dict order
+ *       (kind 1: occupancyCNNMLP.5, .7 first; then motorMlp, cnnMlp, imgMotorMlp, imgMotorMlp2, soundMlp, fusionMlp, mlp_all,
+ *       actor, critic, critic_linear).  Gradient i lies at float offset var_trunk_grad_offset(kind, i) of the one flat d_params
+ *       buffer, whose length is var_trunk_grad_offset(kind, n_params).  var_trunk_n_layers: (n_params - 4) / 2.
+ *   var_trunk_saved_floats / _saved_offset   `saved` holds every layer's activation (M, out) in layer order (i < n_layers), then
+ *       the GRU's output g (M, H) (i = n_layers), then var_gru_seq_fwd's own 5*M*H (i = n_layers + 1).
+ *   var_trunk_fwd   `params`: a HOST array of n_params device pointers in the published order.  11 stage launches (layers of
+ *       one dependency depth share a launch; the residual sums are added on load) + the GRU's 1 + T.  saved may be NULL (a
+ *       forward nobody differentiates: the activations then live in the workspace).
+ *   var_trunk_bwd   given d_value (M, 1), d_actor_features (M, 128), d_hT (N, H), each or all NULL (= zero): d_feat (M, 1152),
+ *       d_occ (M, 288; kind 1), d_hxs (N, H) and every parameter's gradient in d_params; motor_in, sound_in and masks carry no
+ *       gradient.  11 stage launches, each computing dX, dW and db of its layers with the ReLU gate formed on load, +
+ *       var_gru_seq_bwd's.  Stored, not accumulated.  No atomics: equal inputs give equal bits.
+ * Stream-ordered, never synchronise, never allocate.  VAR_ERR_ARG, with a message and nothing launched: a NULL pointer other than
+ * those named, kind not 0 / 1, N outside 1..64, T < 1, T*N above 16384 rows, occ (d_occ) missing for kind 1, a workspace smaller
+ * than var_trunk_workspace_bytes, an output overlapping an input or another output, hxs / saved / workspace not 16-byte aligned. */
+int var_trunk_n_layers(int kind);
+int var_trunk_n_params(int kind);
+long var_trunk_param_floats(int kind, int i);
+long var_trunk_grad_offset(int kind, int i);
+long var_trunk_saved_offset(int kind, int T, int N, int i);
+long var_trunk_saved_floats(int kind, int T, int N);
+long var_trunk_workspace_bytes(int kind, int T, int N);
+int var_trunk_fwd(var_ctx* ctx, void* stream, int kind, const float* const* params, const float* feat,
+                  const float* occ /* kind 1 */, const float* motor_in, const float* sound_in, const float* hxs, const float* masks,
+                  int T, int N, float* value, float* actor_features, float* h_T, float* saved /* may be NULL */, void* workspace,
+                  long workspace_bytes);
+int var_trunk_bwd(var_ctx* ctx, void* stream, int kind, const float* const* params, const float* feat,
+                  const float* occ /* kind 1 */, const float* motor_in, const float* sound_in, const float* masks, int T, int N,
+                  const float* saved, const float* d_value, const float* d_actor_features, const float* d_hT /* each may be NULL */,
+                  float* d_feat, float* d_occ /* kind 1 */, float* d_hxs, float* d_params, void* workspace, long workspace_bytes);
+
 /* The frozen iTHOR encoder's reward step at RL batch sizes -----------------------------------------------------------
  * What the vectorised-env wrapper asks of the frozen pretext model on every environment step
  * (Envs/vec_env/vec_pretext_normalize.py:82-101 getEmbeddings / calcReward, processAI2Thor :125-146): the image embedding,

@@ -1,0 +1,591 @@
+"""CPU restatement of the PPO update's MLP trunk (include/var_hip.h, "The PPO update's MLP trunk"), the checker of csrc/trunk.hip /
+var_amd.trunk_eval: everything between imgCNN's flattened output and the distribution head of armNet_VAR (kind 0,
+models/RL/arm_RL_model.py:102-134) and ai2thorNet_VAR (kind 1, models/RL/ai2thor_RL_model.py:85-115), in torch, in either dtype,
+differentiable by torch autograd, over a dict of parameters named as the base's state_dict names them.
+
+Gates.  A ReLU network's gradient jumps where a pre-activation crosses zero between two precisions, so the restatement takes an
+optional gate pattern: with it every ReLU is z * gate instead of relu(z), a function that is multilinear along its gradients'
+path and has no kink.  The float64 backward a kernel is compared with is taken AT THE KERNEL'S OWN gates; separately, every
+unit whose gate differs from the float64 forward's must have a float64 |pre-activation| within four forward distances of zero,
+and there may be at most MAX_FLIPS of them.  The inputs are chosen so that the yardstick alone has none: a case's seed is the
+first one from its base seed at which torch's fp32 CPU forward and the float64 forward have identical gates (find_seed).
+
+Bounds (tests/rollout_cpu.py's rule): per output, saved activation and gradient array, four times the distance of torch's own fp32
+CPU evaluation from float64 -- the largest over 20 such draws at the tested shape, relative to the array's largest magnitude
+(trunk_distance); five times against the fixture made from the reference.  The yardstick is torch against float64, never the
+kernel."""
+import functools
+import os
+
+import numpy as np
+import torch
+
+from tests.gru_seq_cpu import masked_gru_steps, rel, scale  # noqa: F401
+
+MARGIN, FIXTURE_MARGIN, MAX_FLIPS = 4.0, 5.0, 4
+GRU_PARAMS = ("gru.weight_ih_l0", "gru.weight_hh_l0", "gru.bias_ih_l0", "gru.bias_hh_l0")
+# which of d_value, d_actor_features, d_hT a backward is given
+VARIANTS = {"all": (True, True, True), "no_d_hT": (True, True, False), "no_d_value": (False, True, True),
+            "no_d_actor": (True, False, True)}
+
+
+def hidden(kind):
+    return 1024 if kind else 512
+
+
+@functools.lru_cache(maxsize=None)
+def layers(kind):
+    """(name, in, out, sources, relu) in state_dict order; a source is an input ('feat', 'motor_in', 'sound_in', 'occ'), 'gru'
+    (the recurrent sequence's output over imgMotorMlp.2) or a layer; several sources are summed left to right."""
+    L = []
+    if kind:
+        L += [("occupancyCNNMLP.5", 288, 128, ("occ",), True), ("occupancyCNNMLP.7", 128, 256, ("occupancyCNNMLP.5",), True),
+              ("motorMlp.0", 3, 64, ("motor_in",), True), ("motorMlp.2", 64, 256, ("motorMlp.0",), True)]
+        motor, hid = "motorMlp.2", 64
+    else:
+        L += [("motorMlp.0", 5, 256, ("motor_in",), True), ("motorMlp.2", 256, 512, ("motorMlp.0",), True),
+              ("motorMlp.4", 512, 256, ("motorMlp.2",), True)]
+        motor, hid = "motorMlp.4", 256
+    L += [("cnnMlp.0", 1152, 512, ("feat",), True), ("cnnMlp.2", 512, 256, ("cnnMlp.0",), True),
+          ("imgMotorMlp.0", 256, hid, ("cnnMlp.2", motor) + (("occupancyCNNMLP.7",) if kind else ()), True),
+          ("imgMotorMlp.2", hid, 128, ("imgMotorMlp.0",), True),
+          ("imgMotorMlp2.0", hidden(kind), 256, ("gru",), True),
+          ("soundMlp.0", 3, 128, ("sound_in",), True), ("soundMlp.2", 128, 256, ("soundMlp.0",), True),
+          ("soundMlp.4", 256, 256, ("soundMlp.2",), True),
+          ("fusionMlp.0", 256, 512, ("soundMlp.4", "cnnMlp.2"), True), ("fusionMlp.2", 512, 256, ("fusionMlp.0",), True),
+          ("mlp_all.0", 256, 256, ("fusionMlp.2", "imgMotorMlp2.0"), True), ("mlp_all.2", 256, 128, ("mlp_all.0",), True),
+          ("actor.0", 128, 128, ("mlp_all.2",), True), ("actor.2", 128, 128, ("actor.0",), True),
+          ("critic.0", 128, 128, ("mlp_all.2",), True), ("critic.2", 128, 128, ("critic.0",), True),
+          ("critic_linear", 128, 1, ("critic.2",), False)]
+    return tuple(L)
+
+
+def param_names(kind):
+    """The published parameter order: the four GRU tensors, then weight and bias of every trunk layer in state_dict order."""
+    return list(GRU_PARAMS) + [f"{name}.{w}" for name, *_ in layers(kind) for w in ("weight", "bias")]
+
+
+def input_names(kind):
+    return ("feat", "motor_in", "sound_in", "hxs", "masks") + (("occ",) if kind else ())
+
+
+def params_from_base(base, kind):
+    """name -> fp32 numpy copy of the trunk parameters of a _Base / _IthorBase / armNet_VAR / ai2thorNet_VAR."""
+    sd = base.state_dict()
+    return {k: sd[k].detach().cpu().float().numpy().copy() for k in param_names(kind)}
+
+
+def trunk_forward(kind, P, t, gates=None):
+    """P: name -> tensor, t: the inputs as tensors of the same dtype.  Returns (value, actor_features, h_T, acts, pre): acts holds
+    every layer's activation and 'gru', pre every layer's pre-activation.  gates: layer name -> 0/1 tensor (z * gate replaces
+    relu(z)), or None."""
+    acts = {k: t[k] for k in ("feat", "motor_in", "sound_in", "occ") if k in t}
+    pre, h_T = {}, None
+    for name, _i, _o, src, relu in layers(kind):
+        if src == ("gru",):
+            acts["gru"], h_T = masked_gru_steps(acts["imgMotorMlp.2"], t["hxs"], t["masks"], *(P[k] for k in GRU_PARAMS))
+        x = acts[src[0]]
+        for s in src[1:]:
+            x = x + acts[s]
+        z = x @ P[name + ".weight"].t() + P[name + ".bias"]
+        pre[name] = z
+        acts[name] = z if not relu else (torch.relu(z) if gates is None else z * gates[name])
+    return acts["critic_linear"], acts["actor.2"], h_T, acts, pre
+
+
+def trunk_params(kind, seed):
+    """Seeded fp32 parameters of the scale of the reference's gain-sqrt(2) orthogonal initialisation (Gaussian rows: cheap enough
+    for 20 draws of a 3072 x 1024 matrix), every bias non-zero."""
+    g = torch.Generator().manual_seed(seed)
+    rn = lambda *s: torch.randn(*s, generator=g)                  # noqa: E731
+    H = hidden(kind)
+    P = {"gru.weight_ih_l0": rn(3 * H, 128) / 128 ** 0.5, "gru.weight_hh_l0": rn(3 * H, H) / H ** 0.5,
+         "gru.bias_ih_l0": 0.1 * rn(3 * H), "gru.bias_hh_l0": 0.1 * rn(3 * H)}
+    for name, i, o, _src, _relu in layers(kind):
+        P[name + ".weight"] = rn(o, i) * (2.0 / i) ** 0.5
+        P[name + ".bias"] = 0.1 * rn(o)
+    return {k: v.numpy().astype(np.float32) for k, v in P.items()}
+
+
+def trunk_masks(T, N, g):
+    """0/1 masks (T, N): a zero at t = 0, a step where every env is zero, single zeros, and one at the last step."""
+    masks = (torch.rand(T, N, generator=g) < 0.8).float()
+    if T * N == 1:
+        masks[0, 0] = 1.0                                         # (the one state there is reaches the recurrent product)
+        return masks
+    masks[0, 0] = 0.0
+    if T > 2:
+        masks[T // 2, :] = 0.0
+    masks[T - 1, N - 1] = 0.0
+    if N > 1:
+        masks[0, 1] = 1.0
+    return masks
+
+
+def trunk_data(kind, T, N, seed):
+    """Seeded fp32 numpy inputs (feat and occ non-negative, as the convolution stacks' ReLU leaves them) and the three output
+    gradients d_value, d_actor_features, d_hT."""
+    g = torch.Generator().manual_seed(seed + 1_000_003)
+    rn = lambda *s: torch.randn(*s, generator=g)                  # noqa: E731
+    M, H = T * N, hidden(kind)
+    d = {"feat": torch.relu(rn(M, 1152)), "motor_in": rn(M, 3 if kind else 5), "sound_in": rn(M, 3), "hxs": 0.5 * rn(N, H),
+         "masks": trunk_masks(T, N, g).view(M, 1), "d_value": rn(M, 1), "d_actor_features": rn(M, 128), "d_hT": rn(N, H)}
+    if kind:
+        d["occ"] = torch.relu(rn(M, 288))
+    return {k: v.numpy().astype(np.float32) for k, v in d.items()}
+
+
+def trunk_inputs(kind, T, N, seed):
+    """(P, d): trunk_params and trunk_data of one seed."""
+    return trunk_params(kind, seed), trunk_data(kind, T, N, seed)
+
+
+def gates_of(arrays, kind):
+    """layer name -> bool numpy array [activation > 0] from a dict holding 'act.<layer>' (the ReLU layers only)."""
+    return {name: np.asarray(arrays["act." + name]) > 0 for name, *_rest, relu in layers(kind) if relu}
+
+
+def evaluate(kind, P, d, dtype, gates=None, variants=("all",)):
+    """{variant: {...}} on the CPU in `dtype`, float64 numpy arrays: 'value', 'actor_features', 'h_T', 'act.<layer>', 'act.gru',
+    'pre.<layer>' and the gradients 'd_feat', 'd_occ', 'd_hxs', 'd.<parameter>' of sum(value * d_value) + sum(actor_features *
+    d_actor_features) + sum(h_T * d_hT) restricted to the variant's terms.  gates: layer -> 0/1 array, or None for relu."""
+    tt = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dtype)   # noqa: E731
+    Pt = {k: tt(v).requires_grad_() for k, v in P.items() if k in set(param_names(kind))}
+    t = {k: tt(d[k]) for k in input_names(kind)}
+    leaf_names = ["feat", "hxs"] + (["occ"] if kind else [])
+    for k in leaf_names:
+        t[k].requires_grad_()
+    gt = None if gates is None else {k: tt(np.asarray(v, dtype=np.float64)) for k, v in gates.items()}
+    value, feats, h_T, acts, pre = trunk_forward(kind, Pt, t, gt)
+    common = {"value": value, "actor_features": feats, "h_T": h_T, "act.gru": acts["gru"]}
+    for name, *_ in layers(kind):
+        common["act." + name] = acts[name]
+        common["pre." + name] = pre[name]
+    common = {k: v.detach().double().numpy() for k, v in common.items()}
+    leaves = [t[k] for k in leaf_names] + [Pt[k] for k in param_names(kind)]
+    keys = ["d_" + k for k in leaf_names] + ["d." + k for k in param_names(kind)]
+    res = {}
+    for v in variants:
+        use = VARIANTS[v]
+        terms = [(o * tt(d[k])).sum() for o, k, u in zip((value, feats, h_T), ("d_value", "d_actor_features", "d_hT"), use) if u]
+        grads = torch.autograd.grad(sum(terms[1:], terms[0]), leaves, retain_graph=True, allow_unused=True)
+        r = dict(common)
+        for k, leaf, g in zip(keys, leaves, grads):
+            r[k] = (torch.zeros_like(leaf) if g is None else g).detach().double().numpy()
+        res[v] = r
+    return res
+
+
+def same_gates(a, b, kind):
+    ga, gb = gates_of(a, kind), gates_of(b, kind)
+    return all(np.array_equal(ga[k], gb[k]) for k in ga)
+
+
+@functools.lru_cache(maxsize=None)
+def find_seed(kind, T, N, base_seed):
+    """The first seed >= base_seed at which torch's fp32 CPU forward and the float64 forward have identical gates."""
+    for seed in range(base_seed, base_seed + 64):
+        P, d = trunk_inputs(kind, T, N, seed)
+        with torch.no_grad():
+            a = _forward_only(kind, P, d, torch.float64)
+            b = _forward_only(kind, P, d, torch.float32)
+        if same_gates(a, b, kind):
+            return seed
+    raise AssertionError("no seed with identical fp32 / float64 gates in 64 tries")
+
+
+def _forward_only(kind, P, d, dtype):
+    tt = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dtype)   # noqa: E731
+    _, _, _, acts, _ = trunk_forward(kind, {k: tt(v) for k, v in P.items()}, {k: tt(d[k]) for k in input_names(kind)})
+    return {"act." + name: acts[name].numpy() for name, *_ in layers(kind)}
+
+
+COMPARED = ("value", "actor_features", "h_T", "act.", "d_", "d.")
+
+
+def compared_keys(r):
+    return [k for k in r if k.startswith(COMPARED)]
+
+
+@functools.lru_cache(maxsize=None)
+def trunk_distance(kind, T, N, seeds=20, variants=tuple(VARIANTS)):
+    """{variant: {array: distance}}: per array, the largest over `seeds` draws (each the next seed with identical fp32 / float64
+    gates: the yardstick alone has no flipped gate) of rel(torch fp32 CPU evaluation, float64 evaluation) at this shape."""
+    worst = {v: {} for v in variants}
+    seed = 20_000
+    for _ in range(seeds):
+        seed = find_seed(kind, T, N, seed)
+        P, d = trunk_inputs(kind, T, N, seed)
+        ref = evaluate(kind, P, d, torch.float64, variants=variants)
+        t32 = evaluate(kind, P, d, torch.float32, variants=variants)
+        for v in variants:
+            for k in compared_keys(ref[v]):
+                worst[v][k] = max(worst[v].get(k, 0.0), rel(t32[v][k], ref[v][k]))
+                if k.startswith("d.") and ref[v][k].ndim == 2:    # the sums a fixture keeps of a weight gradient, arrays of their own
+                    for tag, axis in ((".rowsum", 1), (".colsum", 0)):
+                        w = rel(t32[v][k].sum(axis), ref[v][k].sum(axis))
+                        worst[v][k + tag] = max(worst[v].get(k + tag, 0.0), w)
+        seed += 1
+    return worst
+
+
+def trunk_bounds(kind, T, N, variant="all", margin=MARGIN):
+    return {k: margin * v for k, v in trunk_distance(kind, T, N)[variant].items()}
+
+
+def flipped_gates(kind, got_gates, ref, dist):
+    """Units whose gate differs from the float64 forward's: (count, the worst |float64 pre-activation| / its allowance), the
+    allowance being MARGIN * the layer's measured forward distance * the layer's largest magnitude."""
+    count, worst = 0, 0.0
+    for name, g in got_gates.items():
+        flips = np.asarray(g).reshape(ref["pre." + name].shape) != (ref["act." + name] > 0)
+        n = int(flips.sum())
+        if n:
+            allow = MARGIN * dist["act." + name] * scale(ref["act." + name])
+            worst = max(worst, float(np.abs(ref["pre." + name][flips]).max()) / allow)
+            count += n
+    return count, worst
+
+
+# ---- the fixtures made from the reference (tests/golden/make_golden_trunk.py) -----------------------------------------------------
+FIXTURE_T, FIXTURE_N, FIXTURE_SEED, ROWS = 7, 5, 453, 16
+FIXTURES = {0: "trunk_kuka_t7.npz", 1: "trunk_ithor_t7.npz"}
+
+
+@functools.lru_cache(maxsize=None)
+def load_fixture(golden_dir, kind):
+    g = dict(np.load(os.path.join(golden_dir, FIXTURES[kind])))
+    extra = os.path.join(golden_dir, FIXTURES[kind].replace(".npz", "_gru.npz"))      # (a committed file stays below 1 MiB)
+    if os.path.exists(extra):
+        g.update(np.load(extra))
+    return g
+
+
+def drop_in_policy(kind, seed, threads=4):
+    """var_amd.ArmNetPolicy / IthorNetPolicy constructed on the CPU at `seed` (Box(2) / Discrete(8) actions).  nn.init.orthogonal_'s
+    QR depends on the thread count and the machine (weights 1e-4 of their size apart), so nothing here compares against numbers
+    made from these weights elsewhere; the thread count is pinned only to keep one machine's runs alike."""
+    import types
+
+    import var_amd
+
+    class Box:                                                    # stand-ins for gym.spaces (the policies read the class name)
+        shape = (2,)
+
+    class Discrete:
+        n = 8
+
+    kw = {'recurrent': True, 'recurrentInputSize': 128, 'recurrentSize': hidden(kind), 'actionHiddenSize': 128}
+    before = torch.get_num_threads()
+    torch.set_num_threads(threads)
+    try:
+        torch.manual_seed(seed)
+        if kind == 0:
+            cfg = types.SimpleNamespace(img_dim=(3, 96, 96), representationDim=3, robotStateDim=2)
+            return var_amd.ArmNetPolicy(None, Box(), config=cfg, base='arm_VAR', base_kwargs=kw)
+        cfg = types.SimpleNamespace(img_dim=(3, 96, 96), representationDim=3)
+        return var_amd.IthorNetPolicy(None, Discrete(), config=cfg, base='ai2thor_VAR', base_kwargs=kw)
+    finally:
+        torch.set_num_threads(before)
+
+
+def check_values(a):
+    f = np.asarray(a, dtype=np.float64).reshape(-1)
+    return np.array([f.sum(), np.abs(f).sum()])
+
+
+def fixture_inputs(kind, g):
+    """(P, d) of a fixture: the parameters are trunk_params at the fixture's seed (checked against the sums the file keeps of what
+    the reference ran with), the data comes from the file."""
+    P = trunk_params(kind, int(g["seed"].item()))
+    for k in param_names(kind):
+        assert np.array_equal(check_values(P[k]), g["check." + k]), k
+    d = {k: g[k].astype(np.float32) for k in input_names(kind) + ("d_value", "d_actor_features", "d_hT")}
+    return P, d
+
+
+def fixture_distances(kind, got, g):
+    """rel() of each array of `got` ('value', 'actor_features', 'h_T', 'd_feat', 'd_occ', 'd_hxs', 'd.<parameter>') from the
+    fixture's.  A weight gradient gives three entries: its every 16th row under its own name, and '<name>.rowsum' / '.colsum', the
+    float64 sums along both axes (every row is covered), each relative to ITS largest magnitude -- a sum that cancels carries a
+    larger relative error than its terms, so trunk_distance measures the yardstick on these arrays too."""
+    res = {}
+    for k, a in got.items():
+        a = np.asarray(a, dtype=np.float64)
+        if "g." + k in g:
+            res[k] = rel(a, g["g." + k])
+        elif "g." + k + ".rows16" in g:
+            res[k] = rel(a[::ROWS], g["g." + k + ".rows16"])
+            res[k + ".rowsum"] = rel(a.sum(1), g["g." + k + ".rowsum"])
+            res[k + ".colsum"] = rel(a.sum(0), g["g." + k + ".colsum"])
+        elif k in g and k in ("value", "actor_features", "h_T"):
+            res[k] = rel(a, g[k])
+    return res
+
+
+# ---- fp32 emulation of csrc/trunk.hip's summation order --------------------------------------------------------------------------
+def _fma(acc, a, b):
+    """fmaf on fp32 arrays through float64 (the product is exact there; the one extra rounding of the sum is far below fp32's)."""
+    return (acc.astype(np.float64) + a.astype(np.float64) * b.astype(np.float64)).astype(np.float32)
+
+
+def emul_product(Pm, Qm):
+    """C (I, J) = sum_k Pm[i, k] Qm[j, k] as a workgroup of trunk_stage_kernel adds it: the chunks of 16 k go to the four waves in
+    turn (chunk u to wave u & 3); within a chunk the e-th matrix instruction chains k = 16 u + 4 lk + e over lk = 0..3; the four
+    waves' tiles are folded as (w0 + w1) + (w2 + w3)."""
+    Pm, Qm = np.ascontiguousarray(Pm, dtype=np.float32), np.ascontiguousarray(Qm, dtype=np.float32)
+    (I, K), J = Pm.shape, Qm.shape[0]
+    parts = []
+    for w in range(4):
+        acc = np.zeros((I, J), np.float32)
+        for u in range(w, (K + 15) // 16, 4):
+            for e in range(4):
+                for lk in range(4):
+                    k = 16 * u + 4 * lk + e
+                    if k < K:
+                        acc = _fma(acc, Pm[:, k, None], Qm[None, :, k])
+        parts.append(acc)
+    return (parts[0] + parts[1]) + (parts[2] + parts[3])
+
+
+def emul_column_sums(G):
+    acc = np.zeros(G.shape[1], np.float32)
+    for row in G:
+        acc = acc + row
+    return acc
+
+
+def _sum_in_order(arrays):
+    x = arrays[0]
+    for a in arrays[1:]:
+        x = x + a
+    return x
+
+
+def emulate(kind, P, d, variants=("all",)):
+    """evaluate()'s result (without 'pre.*') from an fp32 numpy emulation of the kernels' order of additions: operand sums
+    (a0 + a1) + a2 on load, emul_product for every forward product, dX and dW, the bias added after the fold, db in row order; the
+    recurrent sequence itself is torch's fp32 masked_gru_steps and its autograd."""
+    f = np.float32
+    acts = {k: d[k].astype(f) for k in ("feat", "motor_in", "sound_in", "occ") if k in d}
+    L = layers(kind)
+    gp = [torch.from_numpy(P[k].astype(f)).requires_grad_() for k in GRU_PARAMS]
+    x_t = hxs_t = g_t = hT_t = None
+    for name, _i, _o, src, relu in L:
+        if src == ("gru",):
+            x_t = torch.from_numpy(acts["imgMotorMlp.2"]).requires_grad_()
+            hxs_t = torch.from_numpy(d["hxs"].astype(f)).requires_grad_()
+            g_t, hT_t = masked_gru_steps(x_t, hxs_t, torch.from_numpy(d["masks"].astype(f)), *gp)
+            acts["gru"] = g_t.detach().numpy()
+        z = emul_product(_sum_in_order([acts[s] for s in src]), P[name + ".weight"]) + P[name + ".bias"].astype(f)
+        acts[name] = np.maximum(z, f(0)) if relu else z
+    common = {"value": acts["critic_linear"], "actor_features": acts["actor.2"], "h_T": hT_t.detach().numpy(), "act.gru": acts["gru"]}
+    common.update({"act." + name: acts[name] for name, *_ in L})
+    res = {}
+    for v in variants:
+        use_v, use_a, use_h = VARIANTS[v]
+        M = d["feat"].shape[0]
+        r, dx, gru_dx = dict(common), {}, None
+        for li in range(len(L) - 1, -1, -1):
+            name, i, o, src, relu = L[li]
+            incoming = []
+            if name == "critic_linear":
+                incoming.append(d["d_value"].astype(f) if use_v else np.zeros((M, 1), f))
+            if name == "actor.2":
+                incoming.append(d["d_actor_features"].astype(f) if use_a else np.zeros((M, 128), f))
+            if name == "imgMotorMlp.2":
+                obj = (g_t * torch.from_numpy(dx["imgMotorMlp2.0"])).sum()
+                if use_h:
+                    obj = obj + (hT_t * torch.from_numpy(d["d_hT"].astype(f))).sum()
+                gg = torch.autograd.grad(obj, [x_t, hxs_t] + gp, retain_graph=True)
+                gru_dx, r["d_hxs"] = gg[0].numpy(), gg[1].numpy()
+                r.update({"d." + k: t.numpy() for k, t in zip(GRU_PARAMS, gg[2:])})
+                incoming.append(gru_dx)
+            incoming += [dx[c] for c, _ci, _co, csrc, _cr in L if name in csrc]
+            G = _sum_in_order(incoming)
+            if relu:
+                G = np.where(acts[name] > 0, G, f(0))
+            W = P[name + ".weight"].astype(f)
+            if src[0] not in ("motor_in", "sound_in"):
+                dx[name] = emul_product(G, W.T)
+            r["d." + name + ".weight"] = emul_product(G.T, _sum_in_order([acts[s] for s in src]).T)
+            r["d." + name + ".bias"] = emul_column_sums(G)
+            if src == ("feat",):
+                r["d_feat"] = dx[name]
+            if src == ("occ",):
+                r["d_occ"] = dx[name]
+        res[v] = {k: np.asarray(a, dtype=np.float64) for k, a in r.items()}
+    return res
+
+
+# ---- a bound policy with stand-in convolution stacks, for PPO.loss / PPO.update ------------------------------------------------
+# imgCNN becomes Flatten + Linear(192, 1152) + ReLU over (3, 8, 8) images and occupancyCNNMLP[0:5] Flatten + Linear(81, 288) +
+# ReLU (+ two Identity, so that its Linear layers keep the indices 5 and 7): no GPU test here exercises MIOpen.  Q is the policy's
+# named_parameters() as a dict of numpy arrays.
+IMAGE, OCC, CLIP, VCOEF, ECOEF = (3, 8, 8), (1, 9, 9), 0.2, 0.5, 0.01
+
+
+def standin_params(kind, seed, n_act):
+    g = torch.Generator().manual_seed(seed + 77)
+    rn = lambda *s: torch.randn(*s, generator=g).numpy().astype(np.float32)   # noqa: E731
+    Q = {"base." + k: v for k, v in trunk_params(kind, seed).items()}
+    Q["base.imgCNN.1.weight"], Q["base.imgCNN.1.bias"] = rn(1152, 192) * np.float32((2.0 / 192) ** 0.5 * 2), 0.1 * rn(1152)
+    if kind:
+        Q["base.occupancyCNNMLP.1.weight"], Q["base.occupancyCNNMLP.1.bias"] = rn(288, 81) * np.float32((2.0 / 81) ** 0.5 * 2), 0.1 * rn(288)
+        Q["dist.linear.weight"], Q["dist.linear.bias"] = rn(n_act, 128) / np.float32(128 ** 0.5), 0.1 * rn(n_act)
+    else:
+        Q["dist.fc_mean.weight"], Q["dist.fc_mean.bias"] = rn(n_act, 128) / np.float32(128 ** 0.5), 0.1 * rn(n_act)
+        Q["dist.logstd._bias"] = -np.abs(rn(n_act, 1)) * np.float32(0.5)
+    return Q
+
+
+def standin_modules(kind):
+    """(imgCNN, the first five modules of occupancyCNNMLP or None) as nn modules, to be put into a policy's base."""
+    import torch.nn as nn
+    cnn = nn.Sequential(nn.Flatten(), nn.Linear(192, 1152), nn.ReLU())
+    occ = [nn.Flatten(), nn.Linear(81, 288), nn.ReLU(), nn.Identity(), nn.Identity()] if kind else None
+    return cnn, occ
+
+
+def standin_forward(kind, Q, s, gates=None):
+    """Q, s: tensors of one dtype (images already divided by 255).  (value, actor_features, acts): the stand-in convolution
+    stacks, then trunk_forward.  gates: for the trunk's layers only."""
+    feat = torch.relu(s["image"].flatten(1) @ Q["base.imgCNN.1.weight"].t() + Q["base.imgCNN.1.bias"])
+    t = {"feat": feat, "sound_in": s["goal_sound_feat"], "hxs": s["hxs"], "masks": s["masks"]}
+    if kind:
+        t["motor_in"] = s["image_feat"]
+        t["occ"] = torch.relu(s["occupancy"].flatten(1) @ Q["base.occupancyCNNMLP.1.weight"].t() + Q["base.occupancyCNNMLP.1.bias"])
+    else:
+        t["motor_in"] = torch.cat([s["image_feat"], s["robot_pose"]], 1)
+    value, feats, _h, acts, _pre = trunk_forward(kind, {k[5:]: v for k, v in Q.items() if k.startswith("base.")}, t, gates)
+    acts = dict(acts, feat=feat)
+    if kind:
+        acts["occ"] = t["occ"]
+    return value, feats, acts
+
+
+def _dist(kind, Q, feats):
+    if kind:
+        return torch.distributions.Categorical(logits=feats @ Q["dist.linear.weight"].t() + Q["dist.linear.bias"])
+    mean = feats @ Q["dist.fc_mean.weight"].t() + Q["dist.fc_mean.bias"]
+    return torch.distributions.Normal(mean, (torch.zeros_like(mean) + Q["dist.logstd._bias"].t().view(1, -1)).exp())
+
+
+def _logp(kind, dist, actions):
+    if kind:
+        return dist.log_prob(actions.squeeze(-1)).unsqueeze(-1)
+    return dist.log_prob(actions).sum(-1, keepdim=True)
+
+
+def ppo_total(kind, Q, s, gates=None):
+    """The loss lines of models/ppo/algo/ppo.py:55-87 (clipped value loss) over the stand-in policy; returns (total, acts)."""
+    values, feats, acts = standin_forward(kind, Q, s, gates)
+    dist = _dist(kind, Q, feats)
+    logp = _logp(kind, dist, s["actions"])
+    ratio = torch.exp(logp - s["old_logp"])
+    action_loss = -torch.min(ratio * s["adv"], torch.clamp(ratio, 1.0 - CLIP, 1.0 + CLIP) * s["adv"]).mean()
+    vpc = s["value_preds"] + (values - s["value_preds"]).clamp(-CLIP, CLIP)
+    value_loss = 0.5 * torch.max((values - s["returns"]).pow(2), (vpc - s["returns"]).pow(2)).mean()
+    return value_loss * VCOEF + action_loss - dist.entropy().mean() * ECOEF, acts
+
+
+def _tensors(d, dtype):
+    """numpy dict -> tensors: floats in `dtype`, uint8 images divided by 255 in fp32 first (as the binding does), int64 kept."""
+    out = {}
+    for k, v in d.items():
+        t = torch.from_numpy(np.ascontiguousarray(v))
+        out[k] = t if t.dtype == torch.int64 else ((t.float() / 255.0) if t.dtype == torch.uint8 else t).to(dtype)
+    return out
+
+
+def ppo_sample(kind, Q, T, N, n_act, seed):
+    """A minibatch (numpy, recurrent_generator's row order; uint8 images) that keeps every row away from the loss's kinks, as
+    tests/gru_seq_cpu.py's ppo_sample does: ratio within [0.9, 1.1], old value predictions within 0.15 of the values, returns
+    at least 0.5 away."""
+    r = np.random.default_rng(seed)
+    M, f = T * N, np.float32
+    g = torch.Generator().manual_seed(seed)
+    s = {"image": r.integers(0, 256, size=(M,) + IMAGE, dtype=np.uint8), "image_feat": r.normal(size=(M, 3)).astype(f),
+         "goal_sound_feat": r.normal(size=(M, 3)).astype(f), "hxs": (0.5 * r.normal(size=(N, hidden(kind)))).astype(f),
+         "masks": trunk_masks(T, N, g).view(M, 1).numpy(), "adv": r.normal(size=(M, 1)).astype(f)}
+    if kind:
+        s["occupancy"] = ((r.random((M,) + OCC) < 0.3) * 255).astype(np.uint8)
+    else:
+        s["robot_pose"] = r.normal(size=(M, 2)).astype(f)
+    with torch.no_grad():
+        Q64, s64 = _tensors(Q, torch.float64), _tensors(s, torch.float64)
+        values, feats, _ = standin_forward(kind, Q64, s64)
+        dist = _dist(kind, Q64, feats)
+        actions = dist.sample().unsqueeze(-1) if kind else dist.sample().float().double()
+        logp = _logp(kind, dist, actions).numpy()
+    values = values.numpy()
+    sign = lambda: np.where(r.random((M, 1)) < 0.5, -1.0, 1.0)    # noqa: E731
+    s["actions"] = actions.numpy() if kind else actions.numpy().astype(f)
+    s["old_logp"] = (logp + sign() * r.uniform(0.01, 0.09, size=(M, 1))).astype(f)
+    s["value_preds"] = (values + sign() * r.uniform(0.02, 0.15, size=(M, 1))).astype(f)
+    s["returns"] = (values + sign() * r.uniform(0.5, 1.5, size=(M, 1))).astype(f)
+    return s
+
+
+def ppo_grads(kind, Q, s, dtype, gates=None):
+    """({parameter: gradient of the total, float64 numpy}, {'act.<layer>': activations}) on the CPU in `dtype`."""
+    Qt = {k: v.requires_grad_() for k, v in _tensors(Q, dtype).items()}
+    gt = None if gates is None else {k: torch.from_numpy(np.asarray(v, dtype=np.float64)).to(dtype) for k, v in gates.items()}
+    total, acts = ppo_total(kind, Qt, _tensors(s, dtype), gt)
+    grads = torch.autograd.grad(total, list(Qt.values()))
+    acts = {"act." + k: v.detach().double().numpy() for k, v in acts.items()}
+    return {k: g.double().numpy() for k, g in zip(Qt, grads)}, acts
+
+
+def _ppo_gates_agree(kind, a, b):
+    return same_gates(a, b, kind) and all(np.array_equal(a["act." + k] > 0, b["act." + k] > 0) for k in ("feat", "occ") if "act." + k in a)
+
+
+@functools.lru_cache(maxsize=None)
+def find_ppo_seed(kind, T, N, n_act, base_seed):
+    """The first seed at which the stand-in policy's fp32 CPU and float64 forwards have identical gates (both stand-in stacks'
+    included)."""
+    for seed in range(base_seed, base_seed + 64):
+        Q = standin_params(kind, seed, n_act)
+        s = ppo_sample(kind, Q, T, N, n_act, seed + 500)
+        with torch.no_grad():
+            a = ppo_total(kind, _tensors(Q, torch.float64), _tensors(s, torch.float64))[1]
+            b = ppo_total(kind, _tensors(Q, torch.float32), _tensors(s, torch.float32))[1]
+        a, b = ({"act." + k: v.numpy() for k, v in x.items()} for x in (a, b))
+        if _ppo_gates_agree(kind, a, b):
+            return seed
+    raise AssertionError("no seed with identical fp32 / float64 gates in 64 tries")
+
+
+@functools.lru_cache(maxsize=None)
+def ppo_distance(kind, T, N, n_act, seeds=20):
+    """Per parameter of the stand-in policy, the largest over `seeds` draws of rel(torch fp32 CPU gradient, float64 gradient)."""
+    worst, seed = {}, 30_000
+    for _ in range(seeds):
+        seed = find_ppo_seed(kind, T, N, n_act, seed)
+        Q = standin_params(kind, seed, n_act)
+        s = ppo_sample(kind, Q, T, N, n_act, seed + 500)
+        g64, g32 = ppo_grads(kind, Q, s, torch.float64)[0], ppo_grads(kind, Q, s, torch.float32)[0]
+        for k in g64:
+            worst[k] = max(worst.get(k, 0.0), rel(g32[k], g64[k]))
+        seed += 1
+    return worst
+
+
+def module_from_params(kind, P):
+    """An nn.Module with the base's attribute tree (gru, the Sequentials with their Linear layers at the reference's indices,
+    critic_linear) holding P: what trunk_eval takes as `base`.  No initialiser runs."""
+    import torch.nn as nn
+    base = nn.Module()
+    base.gru = nn.GRU(128, hidden(kind))
+    seqs = {}
+    for name, i, o, _src, _relu in layers(kind):
+        if "." not in name:
+            setattr(base, name, nn.Linear(i, o))
+            continue
+        seq, idx = name.split(".")
+        seqs.setdefault(seq, {})[int(idx)] = nn.Linear(i, o)
+    for seq, lin in seqs.items():
+        setattr(base, seq, nn.Sequential(*(lin.get(i, nn.Identity()) for i in range(max(lin) + 2))))
+    base.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(P[k])) for k in param_names(kind)})
+    return base

@@ -19,3 +19,4 @@ from .ops import inbatch_contrastive_loss, mfcc, mfcc_psf, triplet_margin_loss  
 from .reward import IntrinsicReward, ReturnNormalizer, RunningMeanStd  # noqa: F401
 from .rollout import PPO, RolloutStorage, ppo_loss  # noqa: F401
 from .gru_seq import bind_forward_gru, forward_gru, masked_gru  # noqa: F401
+from .trunk import bind_trunk, trunk_eval  # noqa: F401

@@ -8,7 +8,8 @@ capture(num_envs) returns an ActStep: the same act() as ONE replayed HIP graph o
 var_policy_dist (csrc/policy_dist.hip: sampling from a seeded on-device generator or the mode, the log-probabilities and
 the carry of the hidden state) -- for the RL loop's per-step latency; act() itself is unchanged.
 Inference only: evaluate_actions raises -- the PPO update is var_amd.PPO (rollout.py) over the reference Policy, whose
-evaluation forward and backward stay in PyTorch autograd.  GPU only.
+evaluation forward and backward stay in PyTorch autograd -- or var_amd.PPO(var_amd.bind_trunk(policy), ...) over THIS object:
+bind_trunk gives .base a differentiable forward (imgCNN in PyTorch, everything behind it in csrc/trunk.hip).  GPU only.
 
 IthorNetPolicy is the same for base 'ai2thor_VAR' (models/RL/ai2thor_RL_model.py:ai2thorNet_VAR, iTHOR configuration,
 Discrete actions: 64 tensors, var_ithor_policy_forward in csrc/ithor_policy.hip, sampling through

@@ -10,7 +10,7 @@ For t = 0..T-1 with h_{-1} = hxs: h' = h_{t-1} * m_t, then one nn.GRU cell step 
 reference's segmented form exactly (it multiplies all rows by masks[t] wherever some row is 0; elsewhere every mask is 1.0);
 other mask values are multiplied in as they are, which the reference does not do.  GPU only, fp32 only: there is no CPU
 fallback, anything else raises VarHipError before a launch.  Nothing here reads the device, so the op can sit inside a
-torch.cuda.graph capture."""
+torch.cuda.graph capture.  trunk.py runs the same entry points inside the whole trunk's forward and backward (bind_trunk)."""
 import types
 
 import torch

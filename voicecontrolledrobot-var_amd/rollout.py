@@ -256,7 +256,8 @@ class PPO:
     .dist holding .linear (Categorical) or .fc_mean and .logstd._bias (DiagGaussian).  Its forward and backward run in
     PyTorch autograd; clip_grad_norm_ and optim.Adam as the reference.  PPO(var_amd.bind_forward_gru(actor_critic), ...) puts
     the recurrent sequence of that evaluation (NNBase._forward_gru) on var_amd.masked_gru: forward and backward in HIP, no
-    host read inside the update (gru_seq.py)."""
+    host read inside the update (gru_seq.py).  PPO(var_amd.bind_trunk(actor_critic), ...) puts the whole trunk behind imgCNN there,
+    forward and backward (trunk.py), and trains an ArmNetPolicy / IthorNetPolicy in place."""
 
     def __init__(self, actor_critic, clip_param, ppo_epoch, num_mini_batch, value_loss_coef, entropy_coef, lr=None, eps=None,
                  max_grad_norm=None, use_clipped_value_loss=True, config=None):
