@@ -595,7 +595,12 @@ int var_mfcc_psf(var_ctx* ctx, void* stream, const int16_t* pcm, const int* lens
  * such failure mode, so it is reported).
  * var_debug_buffer: address/length of a named workspace buffer ("act1".."act5", "gact1"..,
  * "sact1".."sact4", "gsact1".., "emb", "gemb", "wpack"; "ithor_s1".."ithor_s3", "ithor_gs1".."ithor_gs3") for
- * layer-wise parity tests.
+ * layer-wise parity tests.  The iTHOR model's names, after the "ithor_" prefix (lengths are those of the PLAN's batch; the
+ * saved forward fills the first B images | nclips clips of each, sound-side strides by nclips): a1..a6, p2..p5, ga1..ga6,
+ * gp2..gp5 (image maps, pooled maps, gradients), s1..s3, gs1..gs3 (sound maps; 3 in the (clip, 73, 64, 7) sequence layout),
+ * gi (dir, clip*73 + t, 1536), hb (dir, step 0..73, clip, 512), gh (split-K partials), dgi (as gi), dgh (dir, step, clip,
+ * 1536), sraw / gsraw (clip, 1024), hid_i / ghid_i (B, 128), hid_s1 / ghid_s1 (clip, 128), hid_s2 / ghid_s2 (clip, 64),
+ * raw / graw / emb (3*maxB rows of 3: images from row 0, clips from row maxB).
  * var_debug_ithor_dense: one dense product of the iTHOR model's bf16 mode through the kernel its schedule would pick,
  * C[m + n*M] (+= when `add`) = sum_k A(m,k) B(k,n), A(m,k) = a[m*K + k] if a_kfast else a[k*M + m], B likewise with
  * b[n*K + k] | b[k*N + n]; nsplit > 1 writes split-K slabs C + s*M*N instead (device pointers, fp32).  Returns 1 when

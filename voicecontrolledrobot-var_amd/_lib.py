@@ -232,17 +232,28 @@ class Context:
     def tag_names(self):
         return [self.lib.var_profile_tag_name(t).decode() for t in range(self.lib.var_profile_tag_count())]
 
-    def debug_buffer(self, name):
+    def debug_buffer_length(self, name):
+        p, n = _vp(), _l()
+        self.check(self.lib.var_debug_buffer(self.handle, name.encode(), ctypes.byref(p), ctypes.byref(n)),
+                   "var_debug_buffer")
+        return n.value
+
+    def debug_buffer(self, name, count=None, offset=0):
+        """A copy of the named workspace buffer, or of `count` floats of it from `offset` (a plan for a large batch makes the
+        whole buffer far longer than what a small batch wrote)."""
         import torch
         p, n = _vp(), _l()
         self.check(self.lib.var_debug_buffer(self.handle, name.encode(), ctypes.byref(p), ctypes.byref(n)),
                    "var_debug_buffer")
-        out = torch.empty(n.value, dtype=torch.float32, device=f"cuda:{self.device_index}")
+        count = n.value - offset if count is None else count
+        if offset < 0 or count < 0 or offset + count > n.value:
+            raise VarHipError(f"debug_buffer({name!r}): [{offset}, {offset + count}) is outside its {n.value} floats")
+        out = torch.empty(count, dtype=torch.float32, device=f"cuda:{self.device_index}")
         torch.cuda.synchronize()
         # raw D2D copy through a ctypes-wrapped view is not available; use hipMemcpy via torch's runtime
         rt = ctypes.CDLL("libamdhip64.so")
         rt.hipMemcpy.argtypes = [_vp, _vp, ctypes.c_size_t, _i]
-        rc = rt.hipMemcpy(out.data_ptr(), p, n.value * 4, 3)   # hipMemcpyDeviceToDevice
+        rc = rt.hipMemcpy(out.data_ptr(), (p.value or 0) + 4 * offset, count * 4, 3)   # hipMemcpyDeviceToDevice
         if rc != 0:
             raise VarHipError(f"hipMemcpy failed ({rc})")
         return out

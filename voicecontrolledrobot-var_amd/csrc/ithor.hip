@@ -1161,6 +1161,19 @@ int ithor_debug_buffer(var_ctx* c, const char* name, void** ptr, long* nfloats) 
     if (!strcmp(name, "hb")) { *ptr = st->Hb; *nfloats = 2L * (kSeq + 1) * C2 * kGh; return VAR_OK; }
     if (!strcmp(name, "gh")) { *ptr = st->GH; *nfloats = 2L * (C2 + 2048) * kG3; return VAR_OK; }
     if (!strcmp(name, "gi")) { *ptr = st->GI; *nfloats = 2L * C2 * kSeq * kG3; return VAR_OK; }
+    // the heads and the GRU backward, for the layer-wise tests: hidden activations and the gradients wrt them (after
+    // their ReLU mask), the un-normalised embeddings (3*maxB rows of 3: [img | clips]), the gate-gradient maps
+    if (!strcmp(name, "dgi")) { *ptr = st->DGI; *nfloats = 2L * C2 * kSeq * kG3; return VAR_OK; }
+    if (!strcmp(name, "dgh")) { *ptr = st->DGH; *nfloats = 2L * C2 * kSeq * kG3; return VAR_OK; }
+    if (!strcmp(name, "gsraw")) { *ptr = st->gsraw; *nfloats = C2 * kSRaw; return VAR_OK; }
+    if (!strcmp(name, "raw")) { *ptr = st->raw; *nfloats = 9L * st->maxB; return VAR_OK; }
+    if (!strcmp(name, "graw")) { *ptr = st->graw; *nfloats = 9L * st->maxB; return VAR_OK; }
+    if (!strcmp(name, "hid_i")) { *ptr = st->hid_i; *nfloats = 128L * st->maxB; return VAR_OK; }
+    if (!strcmp(name, "ghid_i")) { *ptr = st->ghid_i; *nfloats = 128L * st->maxB; return VAR_OK; }
+    if (!strcmp(name, "hid_s1")) { *ptr = st->hid_s1; *nfloats = C2 * 128; return VAR_OK; }
+    if (!strcmp(name, "ghid_s1")) { *ptr = st->ghid_s1; *nfloats = C2 * 128; return VAR_OK; }
+    if (!strcmp(name, "hid_s2")) { *ptr = st->hid_s2; *nfloats = C2 * 64; return VAR_OK; }
+    if (!strcmp(name, "ghid_s2")) { *ptr = st->ghid_s2; *nfloats = C2 * 64; return VAR_OK; }
     VAR_SET_ERR(c, "var_debug_buffer: unknown iTHOR buffer '%s'", name);
     return VAR_ERR_ARG;
 }
