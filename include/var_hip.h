@@ -534,6 +534,54 @@ int var_trunk_bwd(var_ctx* ctx, void* stream, int kind, const float* const* para
                   const float* saved, const float* d_value, const float* d_actor_features, const float* d_hT /* each may be NULL */,
                   float* d_feat, float* d_occ /* kind 1 */, float* d_hxs, float* d_params, void* workspace, long workspace_bytes);
 
+/* The actor-critics' convolution stacks, forward and backward --------------------------------------------------------------
+ * What PPO.update evaluates in front of the trunk above, on a minibatch of B = T*N observations.  Every convolution is 3 x 3
+ * and followed by ReLU; "+pool" is MaxPool2d(2, 2); the output is the last map flattened as NCHW (Flatten()):
+ *   kind 0  armNet_VAR.imgCNN, the 96 x 96 branch of buildCNN (models/RL/arm_RL_model.py:22-34): 3->32, 32->32 +pool, 32->64,
+ *           64->64 +pool, 64->128, 128->128 +pool (stride 1, padding 1), 128->256 (stride 2, padding 0), 256->128 (stride 1,
+ *           padding 0): image (B, 3, 96, 96) -> feat (B, 1152).  The other branch of buildCNN (7 x 7 filter, 120 x 160) has no
+ *           kind: it is not implemented.
+ *   kind 1  ai2thorNet_VAR.imgCNN (models/RL/ai2thor_RL_model.py:16-25): 3->32, 32->32 +pool, 32->64 +pool, 64->64 +pool,
+ *           64->128 +pool (stride 1, padding 1), 128->128 (stride 2, padding 1): image (B, 3, 96, 96) -> feat (B, 1152).
+ *   kind 2  the two convolutions of occupancyCNNMLP (ai2thor_RL_model.py:34-35): 1->64, 64->32 (stride 2, padding 1):
+ *           image (B, 1, 9, 9) -> feat (B, 288), var_trunk_fwd's `occ`.
+ * fp32.  The image is u8 (divided by 255 on the device, as the encoders' first layer does) or f32, image_bstride >= C*H*W
+ * elements between consecutive images.
+ *   var_convstack_n_params / _param_floats / _grad_offset   the published parameter order: weight (OIHW) and bias of every
+ *       convolution in the module's state_dict order.  Gradient i lies at float offset var_convstack_grad_offset(kind, i) of
+ *       the one flat grads_flat buffer, whose length is var_convstack_grad_offset(kind, n_params).
+ *   var_convstack_saved_floats / _saved_offset   `saved` holds every convolution's post-ReLU map (B, C, H, H), un-pooled where
+ *       a pool follows, in layer order: map j at float offset var_convstack_saved_offset(kind, B, j), j = n_params / 2 gives
+ *       the length.  The last map equals feat.  Every offset is a multiple of four floats: there are no gaps.
+ *   var_convstack_fwd   `params`: a HOST array of n_params device pointers in the published order (the reference's Policy has no
+ *       arena).  One launch per convolution, one per pool, one copy.  saved may be NULL (a forward nobody differentiates: the
+ *       maps then live in the workspace).
+ *   var_convstack_bwd   given d_feat (B, 1152 | 288) and the `saved` of the forward over the same params and image: every
+ *       weight and bias gradient into grads_flat, stored, not accumulated.  There is NO gradient for the image or the occupancy
+ *       map -- the observations carry none in PPO -- so the first convolution has no data-gradient launch.  The pool backward
+ *       routes a cell's gradient to the first maximum of its window in scan order and drops it where that maximum is not
+ *       positive (PyTorch's rule).  Split-K partial sums go to the workspace and are added in slab order by fold launches; the
+ *       split is a function of the shape alone.  No atomics: equal inputs give equal bits.
+ * Stream-ordered, never synchronise, never allocate, read nothing back from the device (capturable).  Limits: B in 1..1024.
+ * The gather-GEMM engine addresses an operand by 32-bit byte offsets from its base and divides k (and pixel) indices below
+ * 2^24: at B = 1024 the largest operand, a (B, 32, 96, 96) map, is 1.2e9 bytes and the largest index, B * 96 * 96, is 9.4e6.
+ * VAR_ERR_ARG, with a message that starts with the entry's name and nothing launched or written: kind not 0..2, B outside
+ * 1..1024, a NULL pointer other than `saved` of the forward (a NULL entry of params included), image_bstride below C*H*W or a
+ * batch of images of 4 GB or more, a workspace smaller than var_convstack_workspace_bytes, feat / saved / grads_flat /
+ * workspace not 16-byte aligned.  The queries return VAR_ERR_ARG for a refused kind, index or B. */
+int var_convstack_n_params(int kind);
+long var_convstack_param_floats(int kind, int i);
+long var_convstack_grad_offset(int kind, int i);
+long var_convstack_saved_floats(int kind, int B);
+long var_convstack_saved_offset(int kind, int B, int j);
+long var_convstack_workspace_bytes(int kind, int B);
+int var_convstack_fwd(var_ctx* ctx, void* stream, int kind, const float* const* params, const void* image, int image_is_u8,
+                      long image_bstride, int B, float* feat, float* saved /* may be NULL */, void* workspace,
+                      long workspace_bytes);
+int var_convstack_bwd(var_ctx* ctx, void* stream, int kind, const float* const* params, const void* image, int image_is_u8,
+                      long image_bstride, int B, const float* saved, const float* d_feat, float* grads_flat, void* workspace,
+                      long workspace_bytes);
+
 /* The frozen iTHOR encoder's reward step at RL batch sizes -----------------------------------------------------------
  * What the vectorised-env wrapper asks of the frozen pretext model on every environment step
  * (Envs/vec_env/vec_pretext_normalize.py:82-101 getEmbeddings / calcReward, processAI2Thor :125-146): the image embedding,

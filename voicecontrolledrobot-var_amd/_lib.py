@@ -97,6 +97,14 @@ _SIGNATURES = {
     "var_trunk_workspace_bytes": (_l, [_i, _i, _i]),
     "var_trunk_fwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _l]),
     "var_trunk_bwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l]),
+    "var_convstack_n_params": (_i, [_i]),
+    "var_convstack_param_floats": (_l, [_i, _i]),
+    "var_convstack_grad_offset": (_l, [_i, _i]),
+    "var_convstack_saved_floats": (_l, [_i, _i]),
+    "var_convstack_saved_offset": (_l, [_i, _i, _i]),
+    "var_convstack_workspace_bytes": (_l, [_i, _i]),
+    "var_convstack_fwd": (_i, [_vp, _vp, _i, _vp, _vp, _i, _l, _i, _vp, _vp, _vp, _l]),
+    "var_convstack_bwd": (_i, [_vp, _vp, _i, _vp, _vp, _i, _l, _i, _vp, _vp, _vp, _vp, _l]),
     "var_ithor_reward_plan": (_i, [_vp, _i, _i]),
     "var_ithor_reward_pack": (_i, [_vp, _vp, _vp]),
     "var_ithor_reward_step": (_i, [_vp, _vp, _vp, _vp, _i, _l, _vp, _i, _vp, _vp, _vp]),
