@@ -649,6 +649,15 @@ int var_mfcc_psf(var_ctx* ctx, void* stream, const int16_t* pcm, const int* lens
  * gi (dir, clip*73 + t, 1536), hb (dir, step 0..73, clip, 512), gh (split-K partials), dgi (as gi), dgh (dir, step, clip,
  * 1536), sraw / gsraw (clip, 1024), hid_i / ghid_i (B, 128), hid_s1 / ghid_s1 (clip, 128), hid_s2 / ghid_s2 (clip, 64),
  * raw / graw / emb (3*maxB rows of 3: images from row 0, clips from row maxB).
+ * The acting forwards' workspaces, after "arm_" (var_armnet_forward) / "ipol_" (var_ithor_policy_forward); lengths are
+ * those of the PLAN's batch, a forward of B rows fills the first B rows of each with B-based strides: a1..a8 / a1..a6 (conv
+ * outputs after ReLU, (B, C, h, h); up to 64 images the band kernels pool inside the launch and a2, a4, a6 / a2..a5 are not
+ * written), p1..p3 / p1..p4 (pooled maps), ipol_ only: occf (B, 288), occ (B, 256), h1 (B, 1024); the per-layer path's (B > 8)
+ * flat_img, motor, sound, fusion (B, 256), h0 = rnn_hxs * masks (B, H), gi, gh (B, 3H), t0..t3 (B, <= 512 scratch rows: what
+ * its last writer left).  The small-batch chain's handed-over vectors under their schedule's names (CNN0, FLAT, M0, M1,
+ * MOTOR, S0, S1, SOUND, O0, OCC, GH, IM0, X, F0, FUSION, GI, IMR, ALL0, ALL1, C0, C1, A0, AFT; known once a chain launch has
+ * run on the plan): the raw area of 8 rows x width (value, tag) pairs, value in the low word, the launch's epoch in the
+ * high word; "chain": the whole pair area; "sync": the chain's 64 sync words ([3] = the epoch of the next launch).
  * var_debug_ithor_dense: one dense product of the iTHOR model's bf16 mode through the kernel its schedule would pick,
  * C[m + n*M] (+= when `add`) = sum_k A(m,k) B(k,n), A(m,k) = a[m*K + k] if a_kfast else a[k*M + m], B likewise with
  * b[n*K + k] | b[k*N + n]; nsplit > 1 writes split-K slabs C + s*M*N instead (device pointers, fp32).  Returns 1 when

@@ -133,6 +133,10 @@ struct Workspace {
                                    // launch, [4] sticky: some launch timed out since the last clear
     c3f::f32x4* wpk = nullptr;     // the band convolutions' filters in MFMA A-fragment order (c3f.h), re-packed per forward
     c3f::PackDesc pack{};
+    // host-side record of the last chain launch's handed-over vectors, by their schedule's names (var_debug_buffer)
+    struct ChainVec { const char* name; float* ptr; int width; };
+    ChainVec cvec[kChainBufs];
+    int ncvec = 0;
 
     // the pieces both models have, after a model's own feature maps: hidden size rh, nchain floats of chain area
     void take_shared(Take& t, int rh, long nchain) {
@@ -159,6 +163,24 @@ int ws_alloc(var_ctx* c, Workspace* st, F lay) {
     VAR_HIP_CHECK(c, hipMemcpy(st->sync, init, sizeof(init), hipMemcpyHostToDevice));
     return VAR_OK;
 }
+
+// var_debug_buffer: the pieces both workspaces have, lengths those of the PLAN's batch.  A chain vector (by the name its
+// schedule gives it, once a chain launch has run on this plan) is its raw area of (value, tag) pairs, [kChainRows][width] x 2
+// words.  1 = found.
+inline int ws_debug_buffer(const Workspace* st, int rh, const char* name, void** ptr, long* nfloats) {
+    const long B = st->maxB;
+    const struct { const char* name; float* p; long n; } fixed[] = {
+        {"t0", st->t0, B * 512}, {"t1", st->t1, B * 512}, {"t2", st->t2, B * 512}, {"t3", st->t3, B * 512},
+        {"flat_img", st->flat_img, B * 256}, {"motor", st->motor, B * 256}, {"sound", st->sound, B * 256}, {"fusion", st->fusion, B * 256},
+        {"h0", st->h0, B * rh}, {"gi", st->gi, B * 3 * rh}, {"gh", st->gh, B * 3 * rh}, {"sync", (float*)st->sync, 64},
+        {"chain", st->chain, st->chain_floats}};
+    for (auto& f : fixed)
+        if (!strcmp(name, f.name)) { *ptr = f.p; *nfloats = f.n; return 1; }
+    for (int i = 0; i < st->ncvec; ++i)
+        if (!strcmp(name, st->cvec[i].name)) { *ptr = st->cvec[i].ptr; *nfloats = 2L * kChainRows * st->cvec[i].width; return 1; }
+    return 0;
+}
+#define CHAIN_VEC(id, width) {id, width, #id}
 
 // ---- the entry points' common parts; fn: the C function's name for the message, model: "var_armnet" / "var_ithor_policy"
 // all_set: no pointer the model requires is NULL.  The image is (B, >= 3, 96, 96) with image_bstride elements between images.

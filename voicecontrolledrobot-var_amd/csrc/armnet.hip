@@ -88,10 +88,16 @@ int chain_forward(var_ctx* c, hipStream_t s, arm_state* st, const float* P, cons
     D.buf[A8] = st->a[8]; D.buf[IMGF] = (float*)image_feat; D.buf[POSE] = (float*)robot_pose; D.buf[GOAL] = (float*)goal;
     D.buf[HXS] = (float*)hxs; D.buf[MASK] = (float*)masks; D.buf[HOUT] = hxs_out; D.buf[VALUE] = value; D.buf[AFEAT] = actor_features;
     D.buf[MEAN] = action_mean ? action_mean : scratch(kActions);
-    const int widths[][2] = {{CNN0, 512}, {FLAT, 256}, {M0, 256}, {M1, 512}, {MOTOR, 256}, {S0, 128}, {S1, 256}, {SOUND, 256}, {GH, 3 * kRh},
-                             {IM0, 256}, {X, kRin}, {F0, 512}, {FUSION, 256}, {GI, 3 * kRh}, {IMR, 256}, {ALL0, 256}, {ALL1, 128}, {C0, 128},
-                             {C1, 128}, {A0, 128}, {AFT, kAct}};
-    for (auto& wd : widths) { D.buf[wd[0]] = scratch(wd[1]); D.tagged |= 1ull << wd[0]; }      // handed over inside the launch
+    const struct { int id, width; const char* name; } widths[] = {
+        CHAIN_VEC(CNN0, 512), CHAIN_VEC(FLAT, 256), CHAIN_VEC(M0, 256), CHAIN_VEC(M1, 512), CHAIN_VEC(MOTOR, 256), CHAIN_VEC(S0, 128),
+        CHAIN_VEC(S1, 256), CHAIN_VEC(SOUND, 256), CHAIN_VEC(GH, 3 * kRh), CHAIN_VEC(IM0, 256), CHAIN_VEC(X, kRin), CHAIN_VEC(F0, 512),
+        CHAIN_VEC(FUSION, 256), CHAIN_VEC(GI, 3 * kRh), CHAIN_VEC(IMR, 256), CHAIN_VEC(ALL0, 256), CHAIN_VEC(ALL1, 128), CHAIN_VEC(C0, 128),
+        CHAIN_VEC(C1, 128), CHAIN_VEC(A0, 128), CHAIN_VEC(AFT, kAct)};
+    st->ncvec = 0;
+    for (auto& wd : widths) {                                                                   // handed over inside the launch
+        D.buf[wd.id] = scratch(wd.width); D.tagged |= 1ull << wd.id;
+        st->cvec[st->ncvec++] = {wd.name, D.buf[wd.id], wd.width};
+    }
     D.b_hxs = HXS; D.b_mask = MASK; D.b_hout = HOUT;
     ChainBuilder cb(D);
     auto stage = [&]() { cb.stage(); };
@@ -138,6 +144,23 @@ int chain_forward(var_ctx* c, hipStream_t s, arm_state* st, const float* P, cons
 }  // namespace
 
 void armnet_free(var_ctx* c) { (void)ws_drop<arm_state>(c, &c->arm, false); }
+
+// var_debug_buffer's "arm_" names: conv outputs a1..a8 (a2 / a4 / a6: the gather-GEMM path only), pooled maps p1..p3, then
+// what both workspaces have (ws_debug_buffer)
+int armnet_debug_buffer(var_ctx* c, const char* name, void** ptr, long* nfloats) {
+    arm_state* st = (arm_state*)c->arm;
+    if (!st) { VAR_SET_ERR(c, "var_debug_buffer: no var_armnet_plan"); return VAR_ERR_PLAN; }
+    const long B = st->maxB;
+    const int side[9] = {96, 96, 96, 48, 48, 24, 24, 5, 3}, pside[4] = {0, 48, 24, 12}, pch[4] = {0, 32, 64, 128};
+    if ((name[0] == 'a' || name[0] == 'p') && name[1] >= '1' && name[1] <= '8' && !name[2]) {
+        const int l = name[1] - '0';
+        if (name[0] == 'a') { *ptr = st->a[l]; *nfloats = B * kCh[l] * side[l] * side[l]; return VAR_OK; }
+        if (l <= 3) { *ptr = st->p[l]; *nfloats = B * pch[l] * pside[l] * pside[l]; return VAR_OK; }
+    }
+    if (ws_debug_buffer(st, kRh, name, ptr, nfloats)) return VAR_OK;
+    VAR_SET_ERR(c, "var_debug_buffer: unknown armnet buffer '%s'", name);
+    return VAR_ERR_ARG;
+}
 
 extern "C" {
 

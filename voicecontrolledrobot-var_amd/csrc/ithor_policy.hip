@@ -145,10 +145,16 @@ int chain_forward(var_ctx* c, hipStream_t s, pol_state* st, const float* P, cons
     D.buf[A6] = st->a[6]; D.buf[OCCF] = st->occf; D.buf[IMGF] = (float*)image_feat; D.buf[GOAL] = (float*)goal;
     D.buf[HXS] = (float*)hxs; D.buf[MASK] = (float*)masks; D.buf[HOUT] = hxs_out; D.buf[VALUE] = value; D.buf[AFEAT] = actor_features;
     D.buf[LOGITS] = logits ? logits : scratch(kMaxActions);
-    const int widths[][2] = {{CNN0, 512}, {FLAT, 256}, {M0, 64}, {MOTOR, 256}, {S0, 128}, {S1, 256}, {SOUND, 256}, {O0, 128},
-                             {OCC, 256}, {GH, 3 * kRh}, {IM0, 64}, {X, kRin}, {F0, 512}, {FUSION, 256}, {GI, 3 * kRh}, {IMR, 256},
-                             {ALL0, 256}, {ALL1, 128}, {C0, 128}, {C1, 128}, {A0, 128}, {AFT, kAct}};
-    for (auto& wd : widths) { D.buf[wd[0]] = scratch(wd[1]); D.tagged |= 1ull << wd[0]; }      // handed over inside the launch
+    const struct { int id, width; const char* name; } widths[] = {
+        CHAIN_VEC(CNN0, 512), CHAIN_VEC(FLAT, 256), CHAIN_VEC(M0, 64), CHAIN_VEC(MOTOR, 256), CHAIN_VEC(S0, 128), CHAIN_VEC(S1, 256),
+        CHAIN_VEC(SOUND, 256), CHAIN_VEC(O0, 128), CHAIN_VEC(OCC, 256), CHAIN_VEC(GH, 3 * kRh), CHAIN_VEC(IM0, 64), CHAIN_VEC(X, kRin),
+        CHAIN_VEC(F0, 512), CHAIN_VEC(FUSION, 256), CHAIN_VEC(GI, 3 * kRh), CHAIN_VEC(IMR, 256), CHAIN_VEC(ALL0, 256), CHAIN_VEC(ALL1, 128),
+        CHAIN_VEC(C0, 128), CHAIN_VEC(C1, 128), CHAIN_VEC(A0, 128), CHAIN_VEC(AFT, kAct)};
+    st->ncvec = 0;
+    for (auto& wd : widths) {                                                                   // handed over inside the launch
+        D.buf[wd.id] = scratch(wd.width); D.tagged |= 1ull << wd.id;
+        st->cvec[st->ncvec++] = {wd.name, D.buf[wd.id], wd.width};
+    }
     D.b_hxs = HXS; D.b_mask = MASK; D.b_hout = HOUT;
     ChainBuilder cb(D);
     auto job = [&](const Lin& l, int kind, int in0, int in1, int out, int relu, int out2 = -1, int in2 = -1) {
@@ -190,6 +196,27 @@ int chain_forward(var_ctx* c, hipStream_t s, pol_state* st, const float* P, cons
 }  // namespace
 
 void ithor_policy_free(var_ctx* c) { (void)ws_drop<pol_state>(c, &c->ipol, false); }
+
+// var_debug_buffer's "ipol_" names: conv outputs a1..a6 (a2..a5: the gather-GEMM path only), pooled maps p1..p4, the occupancy
+// branch (occf: its convolutions' (B, 288); occ and h1: the per-layer path's (B, 256) and new hidden state), then what both
+// workspaces have (ws_debug_buffer; the per-layer path's "occ" (B, 256) is not the chain's "OCC" pair vector)
+int ithor_policy_debug_buffer(var_ctx* c, const char* name, void** ptr, long* nfloats) {
+    pol_state* st = (pol_state*)c->ipol;
+    if (!st) { VAR_SET_ERR(c, "var_debug_buffer: no var_ithor_policy_plan"); return VAR_ERR_PLAN; }
+    const long B = st->maxB;
+    const int pside[5] = {0, 48, 24, 12, 6}, pch[5] = {0, 32, 64, 64, 128};
+    if ((name[0] == 'a' || name[0] == 'p') && name[1] >= '1' && name[1] <= '6' && !name[2]) {
+        const int l = name[1] - '0';
+        if (name[0] == 'a') { *ptr = st->a[l]; *nfloats = B * kCh[l] * kSide[l] * kSide[l]; return VAR_OK; }
+        if (l <= 4) { *ptr = st->p[l]; *nfloats = B * pch[l] * pside[l] * pside[l]; return VAR_OK; }
+    }
+    if (!strcmp(name, "occf")) { *ptr = st->occf; *nfloats = B * kOcc; return VAR_OK; }
+    if (!strcmp(name, "occ")) { *ptr = st->occ; *nfloats = B * 256; return VAR_OK; }
+    if (!strcmp(name, "h1")) { *ptr = st->h1; *nfloats = B * kRh; return VAR_OK; }
+    if (ws_debug_buffer(st, kRh, name, ptr, nfloats)) return VAR_OK;
+    VAR_SET_ERR(c, "var_debug_buffer: unknown iTHOR policy buffer '%s'", name);
+    return VAR_ERR_ARG;
+}
 
 extern "C" {
 

@@ -397,6 +397,8 @@ int snd2_bf16_dgrad(var_ctx* c, hipStream_t s, const float* w, float* dx, float*
 int snd2_bf16_wgrad(var_ctx* c, hipStream_t s, float* dw, float* slab, int nclips, int maxclips, void* ws);
 int snd3_bf16_wgrad(var_ctx* c, hipStream_t s, float* dw, float* slab, int nclips, int maxclips, void* ws);   // after snd3_bf16_dgrad
 int ithor_debug_buffer(var_ctx* c, const char* name, void** ptr, long* nfloats);
+int armnet_debug_buffer(var_ctx* c, const char* name, void** ptr, long* nfloats);           // armnet.hip: var_debug_buffer's "arm_" names
+int ithor_policy_debug_buffer(var_ctx* c, const char* name, void** ptr, long* nfloats);     // ithor_policy.hip: its "ipol_" names
 
 // gru_bf16.hip: one launch per GRU time step and pass (recurrent product on bf16 MFMA + gate arithmetic), bf16 mode
 long gru_bf16_workspace_bytes(int maxclips);
