@@ -190,6 +190,40 @@ int var_adam_step_graph(var_ctx* ctx, void* stream, float* params, const float* 
                         float weight_decay, int* step_dev, const int* index_table, int row_ints, int n_rows,
                         int* cursor_dev, int* index_row, int ahead);
 
+/* The PPO update's optimiser step over a table of tensors (models/ppo/algo/ppo.py:32,89-91):
+ *     nn.utils.clip_grad_norm_(self.actor_critic.parameters(), self.max_grad_norm)      # norm type 2
+ *     self.optimizer.step()                                  # optim.Adam(lr, eps): weight decay 0, no amsgrad, no maximize
+ * `segs` is a HOST array of 1..256 segments {p, g, m, v, n}: n floats each of a parameter, its gradient, exp_avg and
+ * exp_avg_sq.  It travels to the kernels by value (as var_move_seg), VAR_OPT_MAX_SEGS segments per launch, and is not read after
+ * the call returns.  Launches: the sums of squares (every workgroup leaves the sum over its share of all gradients in a
+ * context buffer: no floating-point atomics), then clip and Adam -- two for a table of up to VAR_OPT_MAX_SEGS segments,
+ * 2 * ceil(n_seg / VAR_OPT_MAX_SEGS) beyond, all sums of squares before any Adam.  Every workgroup of the second kind folds the
+ * sums in the same order, forms total_norm = sqrt(sum) and coef = min(max_norm / (total_norm + 1e-6), 1) as clip_grad_norm_
+ * does (a NaN norm gives a NaN coef), and applies to g' = g * coef
+ *     m' = m + (g' - m) (1 - beta1);  v' = v beta2 + (1 - beta2) g' g';  p' = p - (lr / bc1) m' / (sqrt(v') / sqrt(bc2) + eps)
+ * with bc1, bc2 = 1 - beta^step formed in double from the advanced *step_dev and from *lr_dev on the device, as
+ * var_adam_step_dev.  *step_dev is advanced by one per call (by the first launch, which stream order puts behind the last
+ * call's readers).  total_norm_out (device, may be NULL) receives the UNCLIPPED norm, which is what clip_grad_norm_ returns.
+ * max_norm <= 0: no clip -- no sum-of-squares launch (one thread advances the step instead), coef = 1, total_norm_out is
+ * not written.
+ * The gradients are NOT modified: PyTorch scales them in place, and nothing in PPO.update reads them afterwards.
+ * Which workgroup and thread takes which element depends on the element's number in the table's concatenation and on the
+ * total length alone, so equal inputs give equal bits, and so do the same tensors cut into segments differently (one merged
+ * segment or many small ones, one launch or several): p, m, v and total_norm alike.  Pointers need 4-byte alignment only:
+ * four consecutive elements of one segment are one 16-byte access per array (dword-aligned), elements next to a segment's end
+ * go one by one.  Non-finite gradients behave as in PyTorch: they go through to the parameters, there is no guard word --
+ * look at total_norm_out.
+ * Stream-ordered; never synchronises, allocates or reads back, so the call can be captured (the graph then holds the
+ * table's addresses).  One call at a time per context: the sums live in the context.
+ * VAR_ERR_ARG, nothing launched or written: n_seg outside 1..256; a NULL pointer in a segment, NULL lr_dev or step_dev;
+ * n < 1; a pointer that is not 4-byte aligned; beta1 or beta2 outside [0, 1); eps < 0; NaN in max_norm, a beta or eps; any
+ * two ranges of the table (p, g, m, v of all segments, and the three scalars) that overlap. */
+#define VAR_OPT_MAX_SEGS 64
+typedef struct var_opt_seg { float* p; const float* g; float* m; float* v; long n; } var_opt_seg;
+int var_clip_adam_step(var_ctx* ctx, void* stream, const var_opt_seg* segs /* host */, int n_seg,
+                       float max_norm /* <= 0: no clip */, const float* lr_dev, float beta1, float beta2, float eps,
+                       int* step_dev, float* total_norm_out /* device, 1 float; may be NULL */);
+
 /* Audio front-end: Envs/audioLoader.py:147-157 (torchaudio MFCC branch) + :241-252
  * (processSoundFeat).  pcm: rows of `pcm_stride` int16 samples; output clip i reads row
  * clip_index[i] (NULL: row i) and lens[i] valid samples (<= pcm_stride; 0 = "empty" class =>

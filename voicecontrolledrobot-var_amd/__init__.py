@@ -21,3 +21,4 @@ from .rollout import PPO, RolloutStorage, ppo_loss  # noqa: F401
 from .gru_seq import bind_forward_gru, forward_gru, masked_gru  # noqa: F401
 from .trunk import bind_trunk, trunk_eval  # noqa: F401
 from .convstack import bind_convs, conv_stack_eval  # noqa: F401
+from .optim import ClipAdam  # noqa: F401

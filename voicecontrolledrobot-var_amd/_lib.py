@@ -38,6 +38,11 @@ class MoveSeg(ctypes.Structure):
                 ("src_env_stride", _l), ("dst_env_stride", _l)]
 
 
+class OptSeg(ctypes.Structure):
+    """var_opt_seg of include/var_hip.h (var_clip_adam_step's segment table, a host array)."""
+    _fields_ = [("p", _vp), ("g", _vp), ("m", _vp), ("v", _vp), ("n", _l)]
+
+
 _SIGNATURES = {
     "var_init": (_i, [_i, ctypes.POINTER(_vp)]),
     "var_destroy": (_i, [_vp]),
@@ -58,6 +63,7 @@ _SIGNATURES = {
     "var_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _i]),
     "var_adam_step_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _f, _f, _f, _f, _vp]),
     "var_adam_step_graph": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _f, _f, _f, _f, _vp, _vp, _i, _i, _vp, _vp, _i]),
+    "var_clip_adam_step": (_i, [_vp, _vp, _vp, _i, _f, _vp, _f, _f, _f, _vp, _vp]),
     "var_mfcc": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "var_mfcc_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "var_arm_loss_grad_pcm": (_i, [_vp, _vp, _vp, _vp, _i, _l, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp]),

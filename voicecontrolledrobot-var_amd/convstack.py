@@ -7,7 +7,8 @@ autograd node.
     ppo = PPO(bind_convs(policy), ...)                   # policy.base(obs, hxs, masks): conv_stack_eval, then trunk_eval
 
 bind_convs works on the reference's Policy and on ArmNetPolicy / IthorNetPolicy alike; with it the whole base is evaluated, forward
-and backward, without a PyTorch autograd kernel and without MIOpen.  The op differentiates in the parameters only: the
+and backward, without a PyTorch autograd kernel and without MIOpen (PPO(..., fused_optimizer=True) takes the gradient clip and
+Adam from PyTorch's kernels as well: optim.py).  The op differentiates in the parameters only: the
 observations carry no gradient in PPO.  GPU only, fp32 only: there is no CPU fallback, anything else raises VarHipError before a
 launch.  Nothing here reads the device, so the op can sit inside a torch.cuda.graph capture."""
 import ctypes

@@ -46,13 +46,15 @@ int var_init(int device_id, var_ctx** out) {
     c->default_w.owner = c;
     c->bound = &c->default_w;
     c->wpack = c->default_w.data;
-    if (e == hipSuccess) e = hipMalloc((void**)&c->loss_buf, sizeof(float) * (64 + kPpoPartFloats));
-    if (e == hipSuccess) e = hipMemset(c->loss_buf, 0, sizeof(float) * (64 + kPpoPartFloats));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->loss_buf, sizeof(float) * (64 + kPpoPartFloats + kOptMaxWG + kOptCarryFloats));
+    if (e == hipSuccess) e = hipMemset(c->loss_buf, 0, sizeof(float) * (64 + kPpoPartFloats + kOptMaxWG + kOptCarryFloats));
     c->done_ctr = (unsigned*)(c->loss_buf + 32);
     c->jsig = (unsigned*)(c->loss_buf + 40);          // 16 words
     c->dist_ctr = (unsigned*)(c->loss_buf + 60);
     c->ppo_ctr = (unsigned*)(c->loss_buf + 61);
     c->ppo_part = c->loss_buf + 64;
+    c->opt_part = c->ppo_part + kPpoPartFloats;
+    c->opt_carry = c->opt_part + kOptMaxWG;
     if (e != hipSuccess) {
         snprintf(g_init_err, sizeof(g_init_err), "var_init: %s", hipGetErrorString(e));
         delete c;

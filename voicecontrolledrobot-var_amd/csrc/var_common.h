@@ -100,6 +100,7 @@ enum VarTag {
 constexpr int kProfMaxPairs = 4096;
 constexpr int kPpoMaxWG = 256, kPpoSums = 8;               // var_ppo_head: at most 256 workgroups, 8 sums each (rollout.hip)
 constexpr int kPpoPartFloats = kPpoMaxWG * kPpoSums;
+constexpr int kOptMaxWG = 1024, kOptCarryFloats = 3 * 256;   // var_clip_adam_step: workgroup sums of squares, running sums between its launches (clip_adam.hip)
 
 // One packed weight image per MODEL (var_weights_create / var_weights_bind): a training model and a frozen
 // copy of the encoder can share a device context without trampling each other's kernel-side filters.
@@ -167,6 +168,8 @@ struct var_ctx {
     unsigned* dist_ctr = nullptr; // the same for var_policy_dist's launches of more than one workgroup (policy_dist.hip)
     unsigned* ppo_ctr = nullptr;  // the same for var_ppo_head's (rollout.hip), and its per-workgroup partial sums: kPpoPartFloats
     float* ppo_part = nullptr;
+    float* opt_part = nullptr;    // var_clip_adam_step's workgroup sums of squares (kOptMaxWG) and, behind them, opt_carry: the threads' running
+    float* opt_carry = nullptr;   // sums of a workgroup whose elements lie in two launches of one call (kOptCarryFloats); clip_adam.hip
     // Device-side hand-over between the two streams of a training step (heads.hip, join_signal below): [0] arrivals of the sound
     // heads' forward workgroups, [1] completed launches of that kernel, [2] how many of them the caller's stream has waited for,
     // [3] waits for it that timed out (sticky; var_join_status); [4..7] the same for the conv 3-5 kernel and the side stream

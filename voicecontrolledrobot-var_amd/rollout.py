@@ -17,6 +17,7 @@ import torch.nn as nn
 import torch.optim as optim
 
 from ._lib import Context, MoveSeg, VarHipError, current_stream_handle, ptr
+from .optim import ClipAdam
 
 MAX_SEGS = 16                                                    # VAR_MOVE_MAX_SEGS
 
@@ -254,13 +255,15 @@ class PPO:
     """models/ppo/algo/ppo.py:6-104 over the device-resident RolloutStorage and ppo_loss.  actor_critic: the reference's
     Policy, or any module with is_recurrent, .base(obs, hxs, masks, infer=False) -> (value, actor_features, hxs, extra) and
     .dist holding .linear (Categorical) or .fc_mean and .logstd._bias (DiagGaussian).  Its forward and backward run in
-    PyTorch autograd; clip_grad_norm_ and optim.Adam as the reference.  PPO(var_amd.bind_forward_gru(actor_critic), ...) puts
+    PyTorch autograd; clip_grad_norm_ and optim.Adam as the reference, or -- fused_optimizer=True -- both inside
+    var_amd.ClipAdam.step(): two launches (optim.py), the step count and the learning rate on the device, self.optimizer.param_groups
+    as update_linear_schedule expects them, state_dict in optim.Adam's layout.  PPO(var_amd.bind_forward_gru(actor_critic), ...) puts
     the recurrent sequence of that evaluation (NNBase._forward_gru) on var_amd.masked_gru: forward and backward in HIP, no
     host read inside the update (gru_seq.py).  PPO(var_amd.bind_trunk(actor_critic), ...) puts the whole trunk behind imgCNN there,
     forward and backward (trunk.py), and trains an ArmNetPolicy / IthorNetPolicy in place."""
 
     def __init__(self, actor_critic, clip_param, ppo_epoch, num_mini_batch, value_loss_coef, entropy_coef, lr=None, eps=None,
-                 max_grad_norm=None, use_clipped_value_loss=True, config=None):
+                 max_grad_norm=None, use_clipped_value_loss=True, config=None, fused_optimizer=False):
         self.config = config
         self.actor_critic = actor_critic
         self.clip_param = clip_param
@@ -279,7 +282,12 @@ class PPO:
             self._kind = 1
         else:
             raise NotImplementedError("PPO: actor_critic.dist must be the reference's DiagGaussian or Categorical")
-        self.optimizer = optim.Adam(actor_critic.parameters(), lr=lr, eps=eps)
+        self.fused_optimizer = bool(fused_optimizer)
+        if self.fused_optimizer:
+            self.optimizer = ClipAdam(actor_critic.parameters(), lr=lr, eps=eps, max_norm=max_grad_norm,
+                                      policy=actor_critic if hasattr(actor_critic, "_arena_intact") else None)
+        else:
+            self.optimizer = optim.Adam(actor_critic.parameters(), lr=lr, eps=eps)
 
     def _head(self, feats):
         dist = self.actor_critic.dist
@@ -304,7 +312,8 @@ class PPO:
                 total, value_loss, action_loss, dist_entropy = self.loss(sample)
                 self.optimizer.zero_grad()
                 total.backward()
-                nn.utils.clip_grad_norm_(self.actor_critic.parameters(), self.max_grad_norm)
+                if not self.fused_optimizer:                     # (ClipAdam.step clips inside)
+                    nn.utils.clip_grad_norm_(self.actor_critic.parameters(), self.max_grad_norm)
                 self.optimizer.step()
                 stats.append(torch.stack((value_loss, action_loss, dist_entropy)))
         num_updates = self.ppo_epoch * self.num_mini_batch

@@ -7,7 +7,8 @@ gru_seq.py in the middle -- forward and backward, as one autograd node.
     ppo = PPO(bind_trunk(policy), ...)        # policy.base(obs, hxs, masks) now runs imgCNN in PyTorch, then trunk_eval
 
 bind_trunk works on the reference's Policy and on ArmNetPolicy / IthorNetPolicy alike: with it var_amd.PPO trains the very
-object whose capture() acts (Adam updates the arena in place; the acting graph re-packs per replay).  With bind_trunk the
+object whose capture() acts (Adam -- PyTorch's, or var_amd.ClipAdam with PPO(..., fused_optimizer=True) -- updates the arena in
+place; the acting graph re-packs per replay).  With bind_trunk the
 convolution stacks' evaluation stays in PyTorch autograd; convstack.py's bind_convs puts them into HIP as well
 (conv_stack_eval), and then nothing of the base's evaluation is left to PyTorch autograd kernels.  GPU only, fp32 only: there is no CPU fallback, anything else raises VarHipError
 before a launch.  Nothing here reads the device, so the op can sit inside a torch.cuda.graph capture."""
