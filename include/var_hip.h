@@ -235,6 +235,25 @@ int var_clip_adam_step(var_ctx* ctx, void* stream, const var_opt_seg* segs /* ho
 int var_mfcc(var_ctx* ctx, void* stream, const int16_t* pcm, const int* lens, const int* clip_index,
              int nclips, int pcm_stride, int out_frames, float* out);
 
+/* Clip cache of the front-end above, for a pool of clips that is read again and again (the reference's
+ * VARFineTuneDataset computes each item's MFCC once, dataset.py:94-133).  The CALLER owns both buffers and fills them:
+ *   cache_feats  f32 [rows][out_frames][40], device: row r = what var_mfcc(pcm, lens = cache_lens, clip_index = NULL, nclips =
+ *                rows, out_frames) writes for it;
+ *   cache_lens   int32 [rows], device: the length row r's features were computed for; negative = row r is not cached.
+ * The library only remembers the pointers, between a bind and the next unbind (or bind): a binding is meant to be SCOPED --
+ * bind, enqueue or capture, unbind -- and the buffers must stay alive and unchanged for as long as work enqueued (or a
+ * graph captured) under the binding may run.  While it is in place, every 512/400/160 front-end launch of this context
+ * (var_mfcc, var_mfcc_ex with those parameters, var_arm_loss_grad_pcm) whose pcm, pcm_stride and out_frames equal the bound
+ * ones decides PER SLOT, on the device: slot i is SERVED -- out[i] = cache_feats[row], no transform, the clip's samples are
+ * not read -- when row = clip_index ? clip_index[i] : i lies in [0, rows), lens[i] > 0 and lens[i] == cache_lens[row]; every
+ * other slot (the empty class, another length, a row that is not cached) is computed as without a binding.  Frames are
+ * computed independently of their neighbours, so a served slot holds the very bits a live one gets.  Launches with another
+ * pcm pointer, stride or out_frames, var_mfcc_psf and var_mfcc_ex's other configurations ignore the binding.
+ * VAR_ERR_ARG: a NULL pointer, rows, pcm_stride or out_frames < 1, rows * out_frames >= 2^31. */
+int var_mfcc_cache_bind(var_ctx* ctx, const int16_t* pcm, int rows, int pcm_stride, int out_frames,
+                        const int* cache_lens, const float* cache_feats);
+int var_mfcc_cache_unbind(var_ctx* ctx);
+
 /* The same front-end with the STFT parameters of the dataset a clip comes from (Envs/audioLoader.py:23-31, param_dict:
  * nFFT / int(windowLenTime * fs) / int(windowStepTime * fs)): 512 / 400 / 160 for GoogleCommand, FSC, ESC50, Spatial,
  * Synthetic -- var_mfcc's kernel -- and 1024 / 800 / 640 for NSynth and UrbanSound, or any power-of-two n_fft in

@@ -1,13 +1,42 @@
+"""Duration of the MFCC front-end alone at batch B (default 256 triplets = 512 clips), 20 launches per replayed graph:
+without a clip cache, and under var_mfcc_cache_bind with every / half / none of the slots served (a slot is taken out of
+the cache by marking its pool row "not cached", so the live work is the same clips' own).
+usage: mfcc_time.py [B]"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import var_amd
+from var_amd._lib import Context, ptr
 pool = var_amd.SyntheticTripletPool(2048, hw=84, seed=0, clips_per_class=32).freeze_pairs()
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 i, c, l = pool.next_batch_indices(B)
-for _ in range(5): var_amd.mfcc(pool.clips, l, 100, c)
-torch.cuda.synchronize()
-e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-e0.record()
-for _ in range(50): var_amd.mfcc(pool.clips, l, 100, c)
-e1.record(); torch.cuda.synchronize()
-print(os.environ.get("VAR_HIP_LIB", "default"), "mfcc us/launch (incl. ~5 us of torch/ctypes per call):", e0.elapsed_time(e1) * 1e3 / 50)
+ctx = Context.get(0)
+n, pcm = c.numel(), pool.clips
+out = torch.empty((n, 1, 100, 40), dtype=torch.float32, device="cuda")
+feats = var_amd.mfcc(pcm, pool.clip_len).reshape(-1, 100, 40).contiguous()
+want = var_amd.mfcc(pcm, l, 100, c)
+
+
+def launch():
+    ctx.check(ctx.lib.var_mfcc(ctx.handle, ctx.stream(), ptr(pcm), ptr(l), ptr(c), n, pcm.stride(0), 100, ptr(out)), "var_mfcc")
+
+
+def timed(label, clens=None):
+    if clens is not None:
+        ctx.check(ctx.lib.var_mfcc_cache_bind(ctx.handle, ptr(pcm), pcm.shape[0], pcm.stride(0), 100, ptr(clens), ptr(feats)), "bind")
+    launch()
+    (g,) = ctx.capture([[launch] * 20])
+    ctx.lib.var_mfcc_cache_unbind(ctx.handle)
+    for _ in range(3): g()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(10): g()
+    e1.record(); torch.cuda.synchronize()
+    assert torch.equal(out, want)
+    print(f"{label:28s} {e0.elapsed_time(e1) * 1e3 / 200:6.1f} us per launch (back to back in a replayed graph)")
+
+
+timed("no cache")
+rows = torch.arange(pcm.shape[0], device="cuda")
+for label, keep in (("cache, every slot served", rows >= 0), ("cache, even rows served", rows % 2 == 0), ("cache, no slot served", rows < 0)):
+    timed(label, torch.where(keep, pool.clip_len, torch.full_like(pool.clip_len, -1)).contiguous())

@@ -639,6 +639,24 @@ int var_mfcc(var_ctx* c, void* stream, const int16_t* pcm, const int* lens, cons
     return launch_mfcc(c, (hipStream_t)stream, pcm, lens, clip_index, nclips, pcm_stride, out_frames, out);
 }
 
+int var_mfcc_cache_bind(var_ctx* c, const int16_t* pcm, int rows, int pcm_stride, int out_frames, const int* cache_lens,
+                        const float* cache_feats) {
+    CHECK_CTX(c);
+    if (!pcm || !cache_lens || !cache_feats || rows <= 0 || pcm_stride <= 0 || out_frames <= 0 ||
+        (long)rows * out_frames >= (1L << 31)) {
+        VAR_SET_ERR(c, "var_mfcc_cache_bind: bad argument");
+        return VAR_ERR_ARG;
+    }
+    c->mfcc_cache = {pcm, rows, pcm_stride, out_frames, cache_lens, cache_feats};
+    return VAR_OK;
+}
+
+int var_mfcc_cache_unbind(var_ctx* c) {
+    CHECK_CTX(c);
+    c->mfcc_cache = {nullptr, 0, 0, 0, nullptr, nullptr};
+    return VAR_OK;
+}
+
 int var_mfcc_ex(var_ctx* c, void* stream, const int16_t* pcm, const int* lens, const int* clip_index, int nclips,
                 int pcm_stride, int out_frames, int n_fft, int win_length, int hop_length, float* out) {
     CHECK_CTX(c);

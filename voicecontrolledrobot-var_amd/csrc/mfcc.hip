@@ -131,8 +131,14 @@ static_assert(258 <= PARTOFF && PARTOFF + PARTLEN <= PPITCH && 16 * PARTLEN == 4
 
 typedef float f32x4m __attribute__((ext_vector_type(4)));
 
-struct FrameRef { const int16_t* sig; int p0, N; bool live, interior; };
-struct FrameMeta { int clip, t, N, row; bool inb; };   // the two dependent index loads (lens, clip_index), one tile earlier
+struct FrameRef { const int16_t* sig; int p0, N; bool live, interior; int cfr; };   // cfr: CACHED, a served frame's index in the cache, else -1
+struct FrameMeta { int clip, t, N, row, clen; bool inb; };   // the dependent index loads (lens, clip_index; CACHED: cache_lens), one tile earlier
+
+// A clip cache bound by var_mfcc_cache_bind (CACHED instantiation only): features of pool row r, computed once by this very
+// kernel for cache_lens[r] valid samples, at feats[r][t][:].  A slot whose length equals its row's cached one is SERVED: its
+// frames are copied from the cache instead of transformed (frames are independent of their tile neighbours -- a frame's lanes,
+// its rows of the matrix products and the fixed-order folds --, so the copy holds the bits a live computation gives).
+struct ClipCache { const int* lens; const float* feats; int rows; };
 
 PH_DECL();
 #ifdef VAR_PHASES
@@ -165,10 +171,18 @@ __device__ __forceinline__ float row_sum16(float e) {          // every lane of 
     return e;
 }
 
-template <bool PSF>
+__device__ __forceinline__ ClipCache cache_of() { return ClipCache{nullptr, nullptr, 0}; }
+__device__ __forceinline__ ClipCache cache_of(const ClipCache& cc) { return cc; }
+
+// Bound... = nothing (mfcc_kernel<PSF>: the kernel as it is without a binding, same arguments, same code) or one ClipCache
+template <bool PSF, typename... Bound>
 __global__ void __launch_bounds__(NTHR, 3)
 mfcc_kernel(const int16_t* __restrict__ pcm, const int* __restrict__ lens, const int* __restrict__ clip_index,
-            int pcm_stride, int out_frames, int total_frames, const float* __restrict__ tab, float* __restrict__ out) {
+            int pcm_stride, int out_frames, int total_frames, const float* __restrict__ tab, float* __restrict__ out,
+            const Bound... bound) {
+    constexpr bool CACHED = sizeof...(Bound) != 0;
+    static_assert(sizeof...(Bound) <= 1 && !(PSF && CACHED), "at most one ClipCache, torchaudio flavour only");
+    const ClipCache cc = cache_of(bound...);
     // separate LDS objects, so that the compiler may move a wave's reads of one past its writes of another (with one
     // array the 16 partner-bin reads of the split were each held behind the previous bin's power store)
     extern __shared__ __attribute__((aligned(16))) float lds[];         // window + twiddle tables, transpose tile (dynamic part)
@@ -190,9 +204,9 @@ mfcc_kernel(const int16_t* __restrict__ pcm, const int* __restrict__ lens, const
     float* pf = pw + fi * PPITCH;
 
     const float inv_of = 1.f / (float)out_frames;
-    auto meta_of = [&](int tile) {
+    auto meta_at = [&](int tile, int frame) {           // frame `frame` of tile `tile`
         FrameMeta m;
-        const int f = tile * FT + fi;
+        const int f = tile * FT + frame;
         m.inb = tile < ntiles && f < total_frames;
         // clip = f / out_frames through a float reciprocal (f < 2^23 frames is checked by the launcher) + one correction
         int clip = (int)((float)f * inv_of), t = f - clip * out_frames;
@@ -201,19 +215,25 @@ mfcc_kernel(const int16_t* __restrict__ pcm, const int* __restrict__ lens, const
         m.clip = clip; m.t = t;
         m.N = lens[clip];
         m.row = clip_index ? clip_index[clip] : clip;
+        m.clen = -1;
+        if (CACHED) m.clen = (unsigned)m.row < (unsigned)cc.rows ? cc.lens[m.row] : -1;
         return m;
     };
+    auto meta_of = [&](int tile) { return meta_at(tile, fi); };
     auto frame_of = [&](const FrameMeta& m) {
         FrameRef r;
         r.N = m.N < pcm_stride ? m.N : pcm_stride;
         r.sig = pcm + (size_t)m.row * pcm_stride;
+        // served: neither fetched nor transformed (the cache holds the whole clip's rows, the zero ones past its last frame too)
+        const bool served = CACHED && m.inb && m.N > 0 && m.N == m.clen;
+        r.cfr = served ? m.row * out_frames + m.t : -1;
         if (PSF) {
             const int T = r.N > WIN ? 1 + (r.N - WIN + HOP - 1) / HOP : 1;
             r.live = m.inb && r.N > 0 && m.t < T;
             r.p0 = m.t * HOP;
             r.interior = r.live && r.p0 > 0 && r.p0 + NFFT <= r.N && !(pcm_stride & 1);
         } else {
-            r.live = m.inb && r.N > 0 && m.t < 1 + r.N / HOP;
+            r.live = m.inb && r.N > 0 && m.t < 1 + r.N / HOP && !served;
             r.p0 = m.t * HOP - NFFT / 2;
             r.interior = r.live && r.p0 >= 0 && r.p0 + NFFT <= r.N && !(pcm_stride & 1);
         }
@@ -260,6 +280,30 @@ mfcc_kernel(const int16_t* __restrict__ pcm, const int* __restrict__ lens, const
     uint32_t pm1 = fetch_prev(fr);
     FrameMeta mnext = meta_of(tile + gridDim.x);
     __builtin_amdgcn_sched_barrier(0);
+    int par = 0;
+    if constexpr (CACHED) {
+        // Every frame that is not live is written HERE, before any transform: a served frame is a copy of its row of the cache,
+        // a dead one (the empty class, the rows behind a clip's last frame) zeros.  One thread per output element of the
+        // workgroup's tiles, no barrier and no LDS in between, so the lookups (lens, clip_index -> cache_lens -> the row) of all
+        // of them are in flight together beside the first tile's samples; the main loop below then stores live frames only.
+        // A workgroup without a live frame ends here: it never pays for the tables (2.5 K floats into LDS, 28 B-operand
+        // registers), and with every slot served the launch is a copy.
+        bool any_live = false;
+#pragma unroll 2
+        for (int tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
+#pragma unroll
+            for (int i = 0; i < (FT * NMFCC + NTHR - 1) / NTHR; ++i) {
+                const int e = tid + i * NTHR, frame = e / NMFCC;
+                if (e < FT * NMFCC && tl * FT + frame < total_frames) {
+                    const FrameRef r = frame_of(meta_at(tl, frame));
+                    any_live |= r.live;
+                    if (!r.live)
+                        out[(size_t)tl * FT * NMFCC + e] = r.cfr >= 0 ? cc.feats[(size_t)r.cfr * NMFCC + (e - frame * NMFCC)] : 0.f;
+                }
+            }
+        }
+        if (__syncthreads_or(any_live) == 0) return;
+    }
     // Tables AFTER the first tile's requests: a workgroup lives for only ~4 tiles (768 workgroups), and its start used to be
     // three dependent round trips in a row -- tables, then the clip lookups, then the samples (~12 K cycles, a sixth of its life).
     // Now the lookups and the samples are in flight while the tables are read and written to LDS.
@@ -277,7 +321,6 @@ mfcc_kernel(const int16_t* __restrict__ pcm, const int* __restrict__ lens, const
 #pragma unroll
     for (int s = 0; s < 10; ++s) dctb[s] = tab[TB_DCTB + ((wave < 3 ? wave : 0) * 10 + s) * 64 + lane];
     __syncthreads();
-    int par = 0;
     // (measured: handing the tiles out through a device-wide atomic counter -- to balance the runs of dead tiles of
     //  "empty" clips -- costs more than it balances: 3200 draws on one address take the kernel from 40 to 55 us)
     // (measured, round 4: dealing the tiles by LIVE rank -- every workgroup scans the clips' lengths, a prefix table in LDS, equal
@@ -291,6 +334,7 @@ mfcc_kernel(const int16_t* __restrict__ pcm, const int* __restrict__ lens, const
         // a tile without a single live frame (the "empty" class, dataset.py:37-38, covers whole clips; so does the
         // zero padding of short clips) is all zeros: skip the transform.  The vote is workgroup-uniform.
         if (__syncthreads_or(fr.live) == 0) {
+            if (!CACHED)
             for (int e = tid; e < FT * NMFCC; e += NTHR) {
                 const long o = (long)tile * FT * NMFCC + e;
                 if (o < (long)total_frames * NMFCC) out[o] = 0.f;
@@ -433,6 +477,9 @@ mfcc_kernel(const int16_t* __restrict__ pcm, const int* __restrict__ lens, const
                 const int fo = tile * FT + frame;
                 float val = d[r];
                 if (PSF && coef == 0) { const float e = en_s[par + frame]; val = __logf(e == 0.f ? kPsfEps : e); }    // appendEnergy
+                if (CACHED) {                        // (frames that are not live were written before the loop)
+                    if (coef < NMFCC && fo < total_frames && live_s[par + frame]) out[(size_t)fo * NMFCC + coef] = val;
+                } else
                 if (coef < NMFCC && fo < total_frames) out[(size_t)fo * NMFCC + coef] = live_s[par + frame] ? val : 0.f;
             }
         }
@@ -516,21 +563,24 @@ static int build_tables(var_ctx* c, bool psf, float** dev) {
     VAR_HIP_CHECK(c, hipMalloc((void**)dev, sizeof(float) * TB_TOTAL));
     VAR_HIP_CHECK(c, hipMemcpy(*dev, tb.data(), sizeof(float) * TB_TOTAL, hipMemcpyHostToDevice));
     if (psf) VAR_HIP_CHECK(c, hipFuncSetAttribute((const void*)mfcc_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, MFCC_LDS_BYTES));
-    else VAR_HIP_CHECK(c, hipFuncSetAttribute((const void*)mfcc_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, MFCC_LDS_BYTES));
+    else {
+        VAR_HIP_CHECK(c, hipFuncSetAttribute((const void*)mfcc_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, MFCC_LDS_BYTES));
+        VAR_HIP_CHECK(c, hipFuncSetAttribute((const void*)mfcc_kernel<false, ClipCache>, hipFuncAttributeMaxDynamicSharedMemorySize, MFCC_LDS_BYTES));
+    }
     return VAR_OK;
 }
 
 int mfcc_build_tables(var_ctx* c) { return build_tables(c, false, &c->mfcc_tab); }
 
-template <bool PSF>
+template <bool PSF, typename... Bound>
 static int launch_flavour(var_ctx* c, hipStream_t s, const int16_t* pcm, const int* lens, const int* clip_index, int nclips,
-                          int pcm_stride, int out_frames, const float* tab, float* out, const char* who) {
+                          int pcm_stride, int out_frames, const float* tab, float* out, const char* who, const Bound... bound) {
     const long total = (long)nclips * out_frames;
     if (total > (1L << 23)) { VAR_SET_ERR(c, "%s: %d clips x %d frames is too many", who, nclips, out_frames); return VAR_ERR_ARG; }
     const int ntiles = (int)((total + FT - 1) / FT);
     const int grid = ntiles < 768 ? ntiles : 768;              // persistent: three 44 KB workgroups per CU
-    hipLaunchKernelGGL(mfcc_kernel<PSF>, dim3(grid), dim3(NTHR), MFCC_LDS_BYTES, s, pcm, lens, clip_index, pcm_stride, out_frames,
-                       (int)total, tab, out);
+    hipLaunchKernelGGL((mfcc_kernel<PSF, Bound...>), dim3(grid), dim3(NTHR), MFCC_LDS_BYTES, s, pcm, lens, clip_index, pcm_stride,
+                       out_frames, (int)total, tab, out, bound...);
     VAR_HIP_CHECK(c, hipGetLastError());
     return VAR_OK;
 }
@@ -545,5 +595,11 @@ int launch_mfcc_psf(var_ctx* c, hipStream_t s, const int16_t* pcm, const int* le
 int launch_mfcc(var_ctx* c, hipStream_t s, const int16_t* pcm, const int* lens, const int* clip_index, int nclips,
                 int pcm_stride, int out_frames, float* out) {
     ProfScope prof(c, s, TAG_MFCC);
+    // a bound clip cache serves this call when it was bound for this very pool and frame count; which SLOTS it serves is decided
+    // on the device (lens and clip_index are device data, rewritten between the replays of a captured step)
+    const auto& mc = c->mfcc_cache;
+    if (mc.feats && mc.pcm == pcm && mc.pcm_stride == pcm_stride && mc.out_frames == out_frames)
+        return launch_flavour<false>(c, s, pcm, lens, clip_index, nclips, pcm_stride, out_frames, c->mfcc_tab, out, "var_mfcc",
+                                     ClipCache{mc.lens, mc.feats, mc.rows});
     return launch_flavour<false>(c, s, pcm, lens, clip_index, nclips, pcm_stride, out_frames, c->mfcc_tab, out, "var_mfcc");
 }

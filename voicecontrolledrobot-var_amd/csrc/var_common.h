@@ -183,6 +183,8 @@ struct var_ctx {
     int wg_groups[5] = {0};       // split-K workgroups used by the last image wgrad launches      // sound slabs start here inside `slabs`
     float* loss_buf = nullptr;
     float* mfcc_tab = nullptr;    // window / twiddles / mel / DCT tables
+    // var_mfcc_cache_bind: the caller's clip cache (mfcc.hip), remembered until var_mfcc_cache_unbind; feats == nullptr: none
+    struct { const int16_t* pcm; int rows, pcm_stride, out_frames; const int* lens; const float* feats; } mfcc_cache = {nullptr, 0, 0, 0, nullptr, nullptr};
     // profiling: HIP events around the launches of ONE selected kernel family
     int prof_tag = -1;
     int prof_n = 0;               // pairs recorded since select

@@ -3,6 +3,8 @@ zero_grad -> forward -> TripletMarginLoss -> backward -> Adam.step as fused HIP 
 arenas, per-epoch MultiStepLR (utils.py:42-46), periodic legacy-format checkpoints and
 progress.csv.  Data parallel: one process per GPU, one RCCL all-reduce of the flat gradient
 arena (+ the loss scalar riding in its last slot) per step."""
+import collections
+import contextlib
 import csv
 import os
 
@@ -36,7 +38,10 @@ class VARTrainer:
     with world_size 2 on gloo."""
 
     def __init__(self, model, lr=1e-4, weight_decay=1e-6, betas=(0.9, 0.999), eps=1e-8, margin=1.0,
-                 process_group=None, _ctx=None):
+                 process_group=None, _ctx=None, cache_clips=True, clip_cache_bytes=2 << 30):
+        """cache_clips: keep the MFCC features of every clip of a pool the trainer is handed (computed once, 16 KB per
+        1 s clip) and serve repeated draws from them (_clip_cache); False computes every clip on every step.  A pool whose
+        cache would exceed clip_cache_bytes (2 GiB: about 131 K clips) runs uncached."""
         flat = model.flat_parameters()
         if _ctx is None:
             if not flat.is_cuda:
@@ -45,6 +50,10 @@ class VARTrainer:
         self.model = model
         self.dev = flat.device
         self.ctx = _ctx
+        # the clip cache needs the library's scoped binding (include/var_hip.h: var_mfcc_cache_bind)
+        self.cache_clips = bool(cache_clips) and hasattr(_ctx.lib, "var_mfcc_cache_bind")
+        self.clip_cache_bytes = int(clip_cache_bytes)
+        self._clip_caches = collections.OrderedDict()
         self.lr, self.wd, self.betas, self.eps, self.margin = lr, weight_decay, betas, eps, margin
         self.hw = model.config.img_dim[1]
         # gradient arena with one extra slot for the loss so that ONE all-reduce carries both
@@ -78,6 +87,74 @@ class VARTrainer:
         were changed behind the trainer's back (load_state_dict, an external optimiser: torch's version counters tell).
         The trainer's own Adam keeps the image current by itself."""
         self.weights = self.model.hip_weights(self.ctx)
+
+    # ---- clip cache: a pool clip's MFCC is computed once, not on every draw (the reference's VARFineTuneDataset does the
+    #      same per item, dataset.py:94-133) ----
+    def _clip_cache(self, pcm, clip_len=None, frames=100):
+        """The cache of pool `pcm` (rows of int16 clips), built on first sight with the front-end itself: features of every
+        row for its valid length -- `clip_len` (int32-able tensor, one entry per row) or, without it, the row width, which
+        is what a pool of full-length clips holds.  A slot whose length differs from its row's cached one is computed live
+        by the kernel, so a wrong guess costs time, never bits.  None: feature off, pool over the byte cap, or a layout
+        the front-end would refuse anyway.  Call it outside graph capture (it allocates and launches)."""
+        if not self.cache_clips or pcm.dim() != 2 or pcm.dtype != torch.int16 or pcm.device != self.dev:
+            return None
+        if pcm.stride(1) != 1 or pcm.stride(0) % 2 or pcm.shape[0] < 1:
+            return None
+        rows = int(pcm.shape[0])
+        if rows * (frames * 40 * 4 + 4) > self.clip_cache_bytes or rows * frames >= 1 << 31:
+            return None
+        key = (pcm.data_ptr(), rows, int(pcm.shape[1]), int(pcm.stride(0)), frames)
+        cache = self._clip_caches.get(key)
+        if cache is None:
+            cache = {"pcm": pcm,              # the reference keeps the address from being reused for another tensor
+                     "lens": torch.empty(rows, dtype=torch.int32, device=self.dev),
+                     "feats": torch.empty((rows, frames, 40), dtype=torch.float32, device=self.dev),
+                     "frames": frames, "version": None, "clip_len": None, "len_version": None}
+            self._clip_caches[key] = cache
+            while len(self._clip_caches) > 4:  # (a captured step keeps its own cache alive through its closures)
+                self._clip_caches.popitem(last=False)
+        if clip_len is not None and clip_len is not cache["clip_len"]:
+            if clip_len.numel() != rows:
+                raise VarHipError("clip_len must hold one length per row of pcm")
+            cache["clip_len"], cache["version"] = clip_len, None
+        self._refresh_clips(cache)
+        return cache
+
+    def _refresh_clips(self, cache):
+        """Refill the cache -- the same buffers, in stream order, so a graph captured over them stays valid -- when the pool
+        (or the length tensor) was written since the features were computed: torch's version counters, one host integer
+        each, compared before every eager step and every replay."""
+        if cache is None:
+            return
+        pcm, cl = cache["pcm"], cache["clip_len"]
+        if cache["version"] == pcm._version and (cl is None or cache["len_version"] == cl._version):
+            return
+        c, rows, frames = self.ctx, int(pcm.shape[0]), cache["frames"]
+        if cl is None:
+            cache["lens"].fill_(int(pcm.shape[1]))
+        else:
+            cache["lens"].copy_(cl.reshape(-1).to(device=self.dev, dtype=torch.int32).clamp(min=-1, max=int(pcm.shape[1])))
+        per = max(1, (1 << 23) // frames)                   # var_mfcc takes up to 2^23 output frames per call
+        for r0 in range(0, rows, per):
+            n = min(per, rows - r0)
+            c.check(c.lib.var_mfcc(c.handle, c.stream(), ptr(pcm[r0:]), ptr(cache["lens"][r0:]), None, n, pcm.stride(0),
+                                   frames, ptr(cache["feats"][r0:])), "var_mfcc")
+        cache["version"] = pcm._version
+        cache["len_version"] = None if cl is None else cl._version
+
+    @contextlib.contextmanager
+    def _clips_bound(self, cache):
+        """The library's scoped binding around ONE enqueue (or the capture of one): no binding outlives a trainer call."""
+        if cache is None:
+            yield
+            return
+        c, pcm = self.ctx, cache["pcm"]
+        c.check(c.lib.var_mfcc_cache_bind(c.handle, ptr(pcm), int(pcm.shape[0]), pcm.stride(0), cache["frames"],
+                                          ptr(cache["lens"]), ptr(cache["feats"])), "var_mfcc_cache_bind")
+        try:
+            yield
+        finally:
+            c.check(c.lib.var_mfcc_cache_unbind(c.handle), "var_mfcc_cache_unbind")
 
     @property
     def grads(self):
@@ -161,7 +238,7 @@ class VARTrainer:
             self._g_step.fill_(int(self.step_count))
             self._g_lr.fill_(float(self.lr))
 
-    def _body_grad_pcm(self, images, pcm, idx, Bs, gb):
+    def _body_grad_pcm(self, images, pcm, idx, Bs, gb, cache=None):
         """Closure enqueueing gather + MFCC + fwd + loss + bwd for `Bs` samples whose indices sit PACKED at the head of
         `idx`: [image_index (Bs) | clip_index (2 Bs) | lens (2 Bs)] (a full row is exactly that with Bs = batch; the short
         last batch of an epoch uses the same layout with Bs < batch and the rest of the row unused)."""
@@ -170,11 +247,12 @@ class VARTrainer:
 
         def body():
             self._bind()
-            c.check(c.lib.var_arm_loss_grad_pcm(c.handle, c.stream(), ptr(flat), ptr(images),
-                                                int(images.dtype == torch.uint8), images.stride(0), ptr(img_idx),
-                                                ptr(pcm), pcm.stride(0), ptr(clip_idx), ptr(lens), Bs, self.hw,
-                                                float(self.margin), 1.0 / gb, ptr(self.gbuf),
-                                                self._loss_ptr(), None), "var_arm_loss_grad_pcm")
+            with self._clips_bound(cache):
+                c.check(c.lib.var_arm_loss_grad_pcm(c.handle, c.stream(), ptr(flat), ptr(images),
+                                                    int(images.dtype == torch.uint8), images.stride(0), ptr(img_idx),
+                                                    ptr(pcm), pcm.stride(0), ptr(clip_idx), ptr(lens), Bs, self.hw,
+                                                    float(self.margin), 1.0 / gb, ptr(self.gbuf),
+                                                    self._loss_ptr(), None), "var_arm_loss_grad_pcm")
         return body
 
     def _body_adam(self, table=None, rows=0, row_ints=0, ahead=0):
@@ -192,7 +270,7 @@ class VARTrainer:
                     "var_adam_step_graph")
         return body
 
-    def capture_dataset_step(self, images, pcm, batch, global_batch=None):
+    def capture_dataset_step(self, images, pcm, batch, global_batch=None, clip_len=None):
         """Capture step_from_dataset(images, idx, pcm, clip_idx, lens) once; returns replay(idx_row) where
         idx_row is an int32 tensor of 5*batch entries [image_index | clip_index (2B) | lens (2B)].
         Step count and learning rate live on the device (var_adam_step_dev); set_lr() updates the latter."""
@@ -200,7 +278,8 @@ class VARTrainer:
         self._g_idx = torch.zeros(5 * B, dtype=torch.int32, device=self.dev)
         self._device_scalars(B)
         self.ctx.ensure_plan(B, self.hw)
-        grad = self._body_grad_pcm(images, pcm, self._g_idx, B, self._gb(B, global_batch))
+        cache = self._clip_cache(pcm, clip_len)
+        grad = self._body_grad_pcm(images, pcm, self._g_idx, B, self._gb(B, global_batch), cache)
         adam = self._body_adam()
         if self._collective():                           # the all-reduce stays eager between two graphs
             g_grad, g_adam = self.ctx.capture([[grad], [adam]])
@@ -209,6 +288,7 @@ class VARTrainer:
 
         def replay(idx_row):
             self._bind()
+            self._refresh_clips(cache)
             self._g_idx.copy_(idx_row, non_blocking=True)
             g_grad()
             if g_adam is not None:
@@ -219,7 +299,7 @@ class VARTrainer:
         return replay
 
     def capture_epoch_steps(self, images, pcm, batch, table, global_batch=None, steps_per_epoch=None, tail_batch=0,
-                            tail_global_batch=None):
+                            tail_global_batch=None, clip_len=None):
         """The replayed step with the data-loader cursor on the device too: `table` is an int32 tensor (rows, 5*batch)
         of step rows [image_index | clip_index (2B) | lens (2B)] (one or more shuffled epochs,
         TripletPool.index_table).  Returns (replay, load_table): replay() launches the captured step -- no host-side
@@ -243,6 +323,7 @@ class VARTrainer:
         self._device_scalars(B)
         c = self.ctx
         c.ensure_plan(B, self.hw)
+        cache = self._clip_cache(pcm, clip_len)             # built here, outside capture (clip_len: valid samples per pool row)
         dp = self._collective()
         ahead = 1 if dp else 0
         # data parallel: index_row holds [row k | row k+1]; the audio front-end runs one step ahead (second copy)
@@ -257,7 +338,8 @@ class VARTrainer:
             return bool(tail_batch) and row % steps_per_epoch == steps_per_epoch - 1
 
         if not dp:
-            graphs = [c.capture([[self._body_grad_pcm(images, pcm, self._g_idx, Bs, gb), adam]])[0] for Bs, gb in sizes]
+            graphs = [c.capture([[self._body_grad_pcm(images, pcm, self._g_idx, Bs, gb, cache), adam]])[0]
+                      for Bs, gb in sizes]
 
             def load_table(t):
                 assert t.shape == self._g_table.shape
@@ -268,6 +350,7 @@ class VARTrainer:
 
             def replay():
                 self._bind()
+                self._refresh_clips(cache)
                 graphs[1 if is_tail(state["row"]) else 0]()
                 state["row"] = (state["row"] + 1) % rows
                 self.step_count += 1
@@ -302,8 +385,9 @@ class VARTrainer:
             clip_idx, lens = nxt[Bs:3 * Bs], nxt[3 * Bs:5 * Bs]
 
             def body():
-                c.check(c.lib.var_mfcc(c.handle, c.stream(), ptr(pcm), ptr(lens), ptr(clip_idx), 2 * Bs,
-                                       pcm.stride(0), 100, ptr(self._g_mfcc)), "var_mfcc")
+                with self._clips_bound(cache):
+                    c.check(c.lib.var_mfcc(c.handle, c.stream(), ptr(pcm), ptr(lens), ptr(clip_idx), 2 * Bs,
+                                           pcm.stride(0), 100, ptr(self._g_mfcc)), "var_mfcc")
             return body
 
         body_front(B)()                                    # warm-up outside capture
@@ -358,6 +442,7 @@ class VARTrainer:
             assert t.shape == self._g_table.shape
             self._g_table.copy_(t, non_blocking=True)
             nxt.copy_(t[0], non_blocking=True)
+            self._refresh_clips(cache)
             g_front[1 if is_tail(0) else 0]()              # features of row 0
             cur.copy_(t[0], non_blocking=True)
             nxt.copy_(t[1 % rows], non_blocking=True)
@@ -367,6 +452,7 @@ class VARTrainer:
         def replay():
             row = state["row"]
             self._bind()
+            self._refresh_clips(cache)
             a, b = (1 if is_tail(row) else 0), (1 if is_tail((row + 1) % rows) else 0)
             if one_graph:
                 g_step[(a, b)]()
@@ -402,11 +488,13 @@ class VARTrainer:
         self.adam()
         return self.loss
 
-    def step_from_dataset(self, images, image_index, pcm, clip_index, lens, global_batch=None):
+    def step_from_dataset(self, images, image_index, pcm, clip_index, lens, global_batch=None, clip_len=None,
+                          _cache=True):
         """One step with the data-loader work folded in (var_arm_loss_grad_pcm): sample b reads image row
         image_index[b] of the HBM-resident `images` (N,3,H,H) u8|f32; clips [pos | neg] read rows
         clip_index (2B) of `pcm` (M, n) int16 with lens (2B) valid samples (0 = "empty" class); the MFCC
-        front-end runs inside the step.  Index tensors are int32 on the trainer's device."""
+        front-end runs inside the step.  Index tensors are int32 on the trainer's device.  `pcm` is taken for a pool that is
+        read again and again: its clips' features are cached (_clip_cache; clip_len: valid samples per pool row)."""
         flat = self.model.flat_parameters()
         B = image_index.numel()
         for t in (image_index, clip_index, lens):
@@ -419,11 +507,13 @@ class VARTrainer:
         c = self.ctx
         c.ensure_plan(B, self.hw)
         self._bind()
-        c.check(c.lib.var_arm_loss_grad_pcm(c.handle, c.stream(), ptr(flat), ptr(images),
-                                            int(images.dtype == torch.uint8), images.stride(0), ptr(image_index),
-                                            ptr(pcm), pcm.stride(0), ptr(clip_index), ptr(lens), B, self.hw,
-                                            float(self.margin), 1.0 / self._gb(B, global_batch), ptr(self.gbuf),
-                                            self._loss_ptr(), None), "var_arm_loss_grad_pcm")
+        cache = self._clip_cache(pcm, clip_len) if _cache else None      # (built on the first step over this pool)
+        with self._clips_bound(cache):
+            c.check(c.lib.var_arm_loss_grad_pcm(c.handle, c.stream(), ptr(flat), ptr(images),
+                                                int(images.dtype == torch.uint8), images.stride(0), ptr(image_index),
+                                                ptr(pcm), pcm.stride(0), ptr(clip_index), ptr(lens), B, self.hw,
+                                                float(self.margin), 1.0 / self._gb(B, global_batch), ptr(self.gbuf),
+                                                self._loss_ptr(), None), "var_arm_loss_grad_pcm")
         self.allreduce()
         self.adam()
         return self.loss
@@ -480,7 +570,7 @@ class VARTrainer:
         self.adam()
         return self.loss
 
-    def capture_inbatch_epoch_steps(self, images, pcm, batch, table, tau=0.1):
+    def capture_inbatch_epoch_steps(self, images, pcm, batch, table, tau=0.1, clip_len=None):
         """step_inbatch as a replayed step over the HBM-resident dataset (BASELINE configs[2]): per step the captured
         graphs gather the images of the current index row, run the MFCC front-end, the encoder forward, the
         in-batch-negatives head, the encoder backward and Adam + row fetch.  With one rank everything is ONE graph; with
@@ -494,6 +584,7 @@ class VARTrainer:
         c, dev, world, rank, rccl = self.ctx, self.dev, self.world, self.rank, self.rccl
         flat = self.model.flat_parameters()
         c.ensure_plan(B, self.hw)
+        cache = self._clip_cache(pcm, clip_len)
         self._g_table = torch.empty_like(table)
         self._g_cursor = torch.zeros(1, dtype=torch.int32, device=dev)
         self._g_idx = torch.zeros(row_ints, dtype=torch.int32, device=dev)
@@ -513,8 +604,9 @@ class VARTrainer:
         def body_fwd():
             self._bind()
             torch.index_select(images, 0, self._g_idx[:B], out=img)     # (int32 indices: no widening launch in front)
-            c.check(c.lib.var_mfcc(c.handle, c.stream(), ptr(pcm), ptr(lens), ptr(clip_idx), 2 * B, pcm.stride(0), 100,
-                                   ptr(feats)), "var_mfcc")
+            with self._clips_bound(cache):
+                c.check(c.lib.var_mfcc(c.handle, c.stream(), ptr(pcm), ptr(lens), ptr(clip_idx), 2 * B, pcm.stride(0), 100,
+                                       ptr(feats)), "var_mfcc")
             c.check(c.lib.var_arm_encoder_fwd(c.handle, c.stream(), ptr(flat), ptr(img), int(img.dtype == torch.uint8),
                                               img.stride(0), ptr(feats), ptr(feats[B:]), B, self.hw, ptr(emb[0]), ptr(emb[1]),
                                               ptr(emb[2]), None, None, 1), "var_arm_encoder_fwd")
@@ -545,6 +637,7 @@ class VARTrainer:
 
         def replay():
             self._bind()
+            self._refresh_clips(cache)
             if world == 1:
                 g_all()
             else:
@@ -572,7 +665,7 @@ class VARTrainer:
         B = image.shape[0]
         idx = torch.arange(B, dtype=torch.int32, device=image.device)
         cidx = torch.arange(2 * B, dtype=torch.int32, device=image.device)
-        return self.step_from_dataset(image, idx, pcm, cidx, lens, global_batch)
+        return self.step_from_dataset(image, idx, pcm, cidx, lens, global_batch, _cache=False)   # (new clips on every call)
 
     def _check(self, image, pos, neg):
         for t in (image, pos, neg):
@@ -686,8 +779,9 @@ def train_representation_from_pool(model, pool, epochs, batch, lr=1e-4, weight_d
         tr.set_lr(multistep_lr(lr, milestones, gamma, ep))
         table = pool.epoch_index_table(batch, drop_last)
         if replay is None:
+            kw = {} if is_ithor else {"clip_len": pool.clip_len}
             replay, load_table = tr.capture_epoch_steps(pool.images, pool.clips, batch, table, steps_per_epoch=spe,
-                                                        tail_batch=bt)
+                                                        tail_batch=bt, **kw)
         else:
             load_table(table)
         acc.zero_()
