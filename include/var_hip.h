@@ -249,6 +249,14 @@ int var_mfcc(var_ctx* ctx, void* stream, const int16_t* pcm, const int* lens, co
  * other slot (the empty class, another length, a row that is not cached) is computed as without a binding.  Frames are
  * computed independently of their neighbours, so a served slot holds the very bits a live one gets.  Launches with another
  * pcm pointer, stride or out_frames, var_mfcc_psf and var_mfcc_ex's other configurations ignore the binding.
+ * var_arm_loss_grad_pcm under a binding reads served clips IN PLACE: its sound CNN, forward and backward, takes a served
+ * slot's features from cache_feats[row] and an empty slot's (lens[i] <= 0) from nowhere, and the front-end neither copies nor
+ * zeroes those slots of the library's feature buffer; live slots go through the buffer as before.  Same bits either way; bit 7
+ * of var_set_streams keeps the copy.  LIFETIME: the pool, cache_feats, cache_lens, and the step's lens and clip_index must
+ * stay unchanged from the enqueue of that forward until the last backward of it has run -- the fused step's own, and a later
+ * var_arm_encoder_bwd of the same forward if one is made.  (VARTrainer complies: the captured step's index row is rewritten by
+ * the optimiser launch, behind the join of both branches.)  var_mfcc and var_mfcc_ex hand features to the caller and always
+ * copy.
  * VAR_ERR_ARG: a NULL pointer, rows, pcm_stride or out_frames < 1, rows * out_frames >= 2^31. */
 int var_mfcc_cache_bind(var_ctx* ctx, const int16_t* pcm, int rows, int pcm_stride, int out_frames,
                         const int* cache_lens, const float* cache_feats);
@@ -684,7 +692,9 @@ int var_mfcc_psf(var_ctx* ctx, void* stream, const int16_t* pcm, const int* lens
  * summed durations and the launch count since the select (it synchronises on the events).
  * var_set_streams: which parts of a step leave the caller's stream (bit 0: sound branch forward incl. the in-step MFCC, bit 1:
  * sound CNN backward, bit 6: the training step's forward and backward hand over between their two streams with graph edges
- * again instead of device-side flags, see var_join_status; other bits are ignored); -1 restores the default (3).
+ * again instead of device-side flags, see var_join_status; bit 7: under a clip cache the step's front-end copies served clips
+ * into the feature buffer and zeroes empty ones, as before clips were read in place -- an opt-out that gives a bit-for-bit
+ * reference inside one build, see var_mfcc_cache_bind; other bits are ignored); -1 restores the default (3).
  * 0 puts every kernel on the caller's stream (per-kernel timing).  Returns the previous mask, as stored: passing it back
  * restores it.
  * var_join_status: in a training step recorded under stream capture (var_arm_loss_grad* with all three branches, two
@@ -734,6 +744,11 @@ int var_debug_ithor_gru_drop_workgroup(var_ctx* ctx);
 int var_debug_armnet_drop_workgroup(var_ctx* ctx);
 int var_debug_ithor_dense(var_ctx* ctx, void* stream, int a_kfast, int b_kfast, const float* a, const float* b,
                           float* c, int M, int N, int K, int nsplit, int add);
+/* timing (tools/mfcc_time.py): the front-end launch that var_arm_loss_grad_pcm makes under a clip cache, on its own --
+ * 100 output frames, served and empty slots of `out` (16-byte aligned) are left as they are, live ones written.
+ * VAR_ERR_STATE without a binding for this pcm / pcm_stride. */
+int var_debug_mfcc_in_place(var_ctx* ctx, void* stream, const int16_t* pcm, const int* lens, const int* clip_index,
+                            int nclips, int pcm_stride, float* out);
 
 #ifdef __cplusplus
 }

@@ -1,8 +1,10 @@
 """Duration of the MFCC front-end alone at batch B (default 256 triplets = 512 clips), 20 launches per replayed graph:
 without a clip cache, and under var_mfcc_cache_bind with every / half / none of the slots served (a slot is taken out of
-the cache by marking its pool row "not cached", so the live work is the same clips' own).
+the cache by marking its pool row "not cached", so the live work is the same clips' own); then the in-place form of the cached
+front-end, the launch the training step makes (var_debug_mfcc_in_place: served and empty slots are not written), on the same
+three caches -- where the library has it.
 usage: mfcc_time.py [B]"""
-import os, sys, torch
+import ctypes, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import var_amd
 from var_amd._lib import Context, ptr
@@ -20,7 +22,12 @@ def launch():
     ctx.check(ctx.lib.var_mfcc(ctx.handle, ctx.stream(), ptr(pcm), ptr(l), ptr(c), n, pcm.stride(0), 100, ptr(out)), "var_mfcc")
 
 
-def timed(label, clens=None):
+def launch_in_place():
+    ctx.check(ctx.lib.var_debug_mfcc_in_place(ctx.handle, ctx.stream(), ptr(pcm), ptr(l), ptr(c), n, pcm.stride(0), ptr(out)),
+              "var_debug_mfcc_in_place")
+
+
+def timed(label, clens=None, launch=launch):
     if clens is not None:
         ctx.check(ctx.lib.var_mfcc_cache_bind(ctx.handle, ptr(pcm), pcm.shape[0], pcm.stride(0), 100, ptr(clens), ptr(feats)), "bind")
     launch()
@@ -38,5 +45,14 @@ def timed(label, clens=None):
 
 timed("no cache")
 rows = torch.arange(pcm.shape[0], device="cuda")
-for label, keep in (("cache, every slot served", rows >= 0), ("cache, even rows served", rows % 2 == 0), ("cache, no slot served", rows < 0)):
+legs = (("cache, every slot served", rows >= 0), ("cache, even rows served", rows % 2 == 0), ("cache, no slot served", rows < 0))
+for label, keep in legs:
     timed(label, torch.where(keep, pool.clip_len, torch.full_like(pool.clip_len, -1)).contiguous())
+if hasattr(ctx.lib, "var_debug_mfcc_in_place"):
+    vp, i = ctypes.c_void_p, ctypes.c_int
+    ctx.lib.var_debug_mfcc_in_place.restype, ctx.lib.var_debug_mfcc_in_place.argtypes = i, [vp, vp, vp, vp, vp, i, i, vp]
+    # (`out` holds the copying legs' result, so the check inside timed() also says that what the in-place form leaves out is
+    # exactly what its readers take from the cache or from nowhere: the live slots it writes are the same bits)
+    for label, keep in legs:
+        timed("in place: " + label[7:], torch.where(keep, pool.clip_len, torch.full_like(pool.clip_len, -1)).contiguous(),
+              launch_in_place)

@@ -319,7 +319,7 @@ static constexpr int kSmallMidB = 16;
 // forward; join_requested / capturing: the caller asked for the device-side hand-over and `s` is being captured; dot_armed:
 // var_set_reward_dot armed this forward.
 static FwdPlan plan_encoder_fwd(int H, int B, int save_for_bwd, bool image, bool pos, bool neg, bool finish, bool join_requested,
-                                bool capturing, int streams, bool dot_armed) {
+                                bool capturing, int streams, bool dot_armed, bool front_in_place = false) {
     FwdPlan p;
     const bool fwd_only = save_for_bwd == 2;
     const bool snd = pos || neg;
@@ -344,7 +344,12 @@ static FwdPlan plan_encoder_fwd(int H, int B, int save_for_bwd, bool image, bool
     // small batches (the RL stage's 8 envs) stay on the caller's stream: every kernel is a few us there and a fork / join pair
     // costs more than the overlap gives
     p.fork_ok = (streams & 1) && B > 32;
-    p.mfcc_main = !p.fork_ok;
+    // The in-place front-end (served clips are not copied: a few us of lookups) runs on the caller's stream IN FRONT of the fork:
+    // on the side stream it ended before the image chain's first kernel had got through its queue hand-over, the sound forward
+    // took half of the CUs first and img_head2's persistent workgroups doubled up on the rest (measured: img_head2 36.8 -> 51.7 us,
+    // img_mid3 47.6 -> 59.4, the step 0.264 -> 0.288 ms).  In front of the fork the image chain follows it on the same queue and
+    // it is the sound branch that pays the hand-over, behind img_head2's placement.
+    p.mfcc_main = !p.fork_ok || front_in_place;
     // The device-side hand-over only under stream capture: in a replayed graph both branches sit in the device's queues before
     // either starts, so a wait can only be as long as the other branch's kernels; launched eagerly, a host thread that is
     // descheduled between the two branches' launches would turn into a time-out and a step with stale numbers -- and eagerly the
@@ -368,11 +373,22 @@ static int encoder_fwd(var_ctx* c, hipStream_t s, const float* params, const voi
         neg = c->mfcc_buf + (size_t)B * VAR_MFCC_FRAMES * VAR_MFCC_COEFFS;
     }
     const bool snd = pos || neg;
+    // Where the sound CNN reads each clip slot (clip_src.h).  When the front-end runs HERE, into the library's own buffer, under a
+    // clip cache bound for this pool, served and empty slots are read in place -- from the cache row, from nowhere -- and the
+    // front-end neither copies nor zeroes them: the buffer has no reader but the sound kernels of this forward and its backwards.
+    // (Bit 7 of the stream mask keeps the copy; features handed to outside readers -- var_mfcc, var_mfcc_ex -- are always copied.)
+    ClipSrc src = {pos, neg, B, nullptr, nullptr, nullptr, nullptr, 0, VAR_MFCC_FRAMES};
+    const bool in_place = audio && audio->pcm && !(c->streams & 128) &&
+                          mfcc_cache_matches(c, audio->pcm, audio->pcm_stride, VAR_MFCC_FRAMES);
+    if (in_place) {
+        src.lens = audio->lens; src.clip_index = audio->clip_index;
+        src.cache_lens = c->mfcc_cache.lens; src.cache_feats = c->mfcc_cache.feats; src.cache_rows = c->mfcc_cache.rows;
+    }
     // (decided before the first launch: the image forward's last kernel raises the flag the sound rows wait for)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (join_requested && hipStreamIsCapturing(s, &cap) != hipSuccess) cap = hipStreamCaptureStatusNone;
     const FwdPlan p = plan_encoder_fwd(c->H, B, save_for_bwd, image, pos, neg, finish, join_requested,
-                                       cap == hipStreamCaptureStatusActive, c->streams, dot_armed);
+                                       cap == hipStreamCaptureStatusActive, c->streams, dot_armed, in_place);
     c->fwd_plan = p;
     hipStream_t ss = p.fork_ok ? c->side : s;
     // Launch ORDER matters under graph replay: the chain that is enqueued first after a fork keeps the hardware
@@ -382,7 +398,7 @@ static int encoder_fwd(var_ctx* c, hipStream_t s, const float* params, const voi
     if (snd && audio && audio->pcm) {
         if (!p.mfcc_main) { if ((rc = fork_side(c, s, 0)) != VAR_OK) return rc; forked = true; }
         if ((rc = launch_mfcc(c, p.mfcc_main ? s : ss, audio->pcm, audio->lens, audio->clip_index, 2 * B, audio->pcm_stride,
-                              VAR_MFCC_FRAMES, c->mfcc_buf)) != VAR_OK) return rc;
+                              VAR_MFCC_FRAMES, c->mfcc_buf, in_place)) != VAR_OK) return rc;
     }
     if (snd && p.fork_ok && !forked && (rc = fork_side(c, s, 0)) != VAR_OK) return rc;     // the side stream starts after the caller's prior work
     if (image) {
@@ -394,7 +410,7 @@ static int encoder_fwd(var_ctx* c, hipStream_t s, const float* params, const voi
         }
     }
     if (snd) {
-        if ((rc = launch_snd_fwd(c, ss, params, pos, neg, B)) != VAR_OK) return rc;
+        if ((rc = launch_snd_fwd(c, ss, params, src, B)) != VAR_OK) return rc;
         if ((rc = launch_heads_fwd(c, ss, ss, p, params, B, false, pos != nullptr, neg != nullptr, finish)) != VAR_OK) return rc;
         if (p.fork_ok && !p.dev_join && (rc = join_side(c, s, 0)) != VAR_OK) return rc;
     }
@@ -406,6 +422,7 @@ static int encoder_fwd(var_ctx* c, hipStream_t s, const float* params, const voi
     c->saved_index = image_index;
     c->saved_pos = pos;
     c->saved_neg = neg;
+    c->saved_src = src;
     return VAR_OK;
 }
 
@@ -639,6 +656,17 @@ int var_mfcc(var_ctx* c, void* stream, const int16_t* pcm, const int* lens, cons
     return launch_mfcc(c, (hipStream_t)stream, pcm, lens, clip_index, nclips, pcm_stride, out_frames, out);
 }
 
+// measurement hook (tools/mfcc_time.py): the in-place form of the cached front-end on its own -- the launch the training step
+// makes under a binding; served and empty slots of `out` are left as they are
+int var_debug_mfcc_in_place(var_ctx* c, void* stream, const int16_t* pcm, const int* lens, const int* clip_index, int nclips,
+                            int pcm_stride, float* out) {
+    CHECK_CTX(c);
+    if (!pcm || !lens || !out || nclips <= 0 || pcm_stride <= 0) { VAR_SET_ERR(c, "var_debug_mfcc_in_place: bad argument"); return VAR_ERR_ARG; }
+    if (!mfcc_cache_matches(c, pcm, pcm_stride, VAR_MFCC_FRAMES)) { VAR_SET_ERR(c, "var_debug_mfcc_in_place: no cache bound for this pool"); return VAR_ERR_STATE; }
+    SET_DEVICE(c);
+    return launch_mfcc(c, (hipStream_t)stream, pcm, lens, clip_index, nclips, pcm_stride, VAR_MFCC_FRAMES, out, true);
+}
+
 int var_mfcc_cache_bind(var_ctx* c, const int16_t* pcm, int rows, int pcm_stride, int out_frames, const int* cache_lens,
                         const float* cache_feats) {
     CHECK_CTX(c);
@@ -692,7 +720,8 @@ static int default_streams() { return kDefaultStreams; }
 int var_set_streams(var_ctx* c, int mask) {
     if (!c) return -1;
     const int old = c->streams;
-    c->streams = mask < 0 ? default_streams() : (mask & (3 | 64));   // bit 6: keep the graph edge between the forward's two streams
+    // bit 6: keep the graph edge between the forward's two streams; bit 7: served clips are copied into the feature buffer
+    c->streams = mask < 0 ? default_streams() : (mask & (3 | 64 | 128));
     return old;
 }
 

@@ -20,9 +20,11 @@
 // either end of the clip (reflect padding) take a per-sample path.  Tables are computed once on the host in double.
 #include <math.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "var_common.h"
+#include "clip_src.h"
 
 namespace {
 constexpr int NFFT = 512, WIN = 400, HOP = 160, NMEL = 40, NMFCC = 40, NFREQ = 257;
@@ -139,6 +141,10 @@ struct FrameMeta { int clip, t, N, row, clen; bool inb; };   // the dependent in
 // frames are copied from the cache instead of transformed (frames are independent of their tile neighbours -- a frame's lanes,
 // its rows of the matrix products and the fixed-order folds --, so the copy holds the bits a live computation gives).
 struct ClipCache { const int* lens; const float* feats; int rows; };
+// The same cache for readers that resolve every slot through clip_src.h (the sound CNN of the step the front-end runs in): served
+// and empty slots are neither copied nor zeroed -- their readers take them from the cache row, or from nowhere --, live slots are
+// written exactly as by the copying form, the zero rows behind a live clip's last frame included.
+struct ClipCacheInPlace { ClipCache cc; };
 
 PH_DECL();
 #ifdef VAR_PHASES
@@ -173,14 +179,17 @@ __device__ __forceinline__ float row_sum16(float e) {          // every lane of 
 
 __device__ __forceinline__ ClipCache cache_of() { return ClipCache{nullptr, nullptr, 0}; }
 __device__ __forceinline__ ClipCache cache_of(const ClipCache& cc) { return cc; }
+__device__ __forceinline__ ClipCache cache_of(const ClipCacheInPlace& b) { return b.cc; }
 
-// Bound... = nothing (mfcc_kernel<PSF>: the kernel as it is without a binding, same arguments, same code) or one ClipCache
+// Bound... = nothing (mfcc_kernel<PSF>: the kernel as it is without a binding, same arguments, same code), one ClipCache or one
+// ClipCacheInPlace
 template <bool PSF, typename... Bound>
 __global__ void __launch_bounds__(NTHR, 3)
 mfcc_kernel(const int16_t* __restrict__ pcm, const int* __restrict__ lens, const int* __restrict__ clip_index,
             int pcm_stride, int out_frames, int total_frames, const float* __restrict__ tab, float* __restrict__ out,
             const Bound... bound) {
     constexpr bool CACHED = sizeof...(Bound) != 0;
+    constexpr bool INPLACE = (std::is_same<Bound, ClipCacheInPlace>::value || ... || false);
     static_assert(sizeof...(Bound) <= 1 && !(PSF && CACHED), "at most one ClipCache, torchaudio flavour only");
     const ClipCache cc = cache_of(bound...);
     // separate LDS objects, so that the compiler may move a wave's reads of one past its writes of another (with one
@@ -214,9 +223,9 @@ mfcc_kernel(const int16_t* __restrict__ pcm, const int* __restrict__ lens, const
         if (!m.inb) { clip = 0; t = 0; }
         m.clip = clip; m.t = t;
         m.N = lens[clip];
-        m.row = clip_index ? clip_index[clip] : clip;
+        m.row = clip_row_of(clip_index, clip);
         m.clen = -1;
-        if (CACHED) m.clen = (unsigned)m.row < (unsigned)cc.rows ? cc.lens[m.row] : -1;
+        if (CACHED) m.clen = clip_cached_len(cc.lens, cc.rows, m.row);
         return m;
     };
     auto meta_of = [&](int tile) { return meta_at(tile, fi); };
@@ -225,7 +234,7 @@ mfcc_kernel(const int16_t* __restrict__ pcm, const int* __restrict__ lens, const
         r.N = m.N < pcm_stride ? m.N : pcm_stride;
         r.sig = pcm + (size_t)m.row * pcm_stride;
         // served: neither fetched nor transformed (the cache holds the whole clip's rows, the zero ones past its last frame too)
-        const bool served = CACHED && m.inb && m.N > 0 && m.N == m.clen;
+        const bool served = CACHED && m.inb && clip_served(m.N, m.clen);       // clip_src.h: the readers' rule
         r.cfr = served ? m.row * out_frames + m.t : -1;
         if (PSF) {
             const int T = r.N > WIN ? 1 + (r.N - WIN + HOP - 1) / HOP : 1;
@@ -281,7 +290,30 @@ mfcc_kernel(const int16_t* __restrict__ pcm, const int* __restrict__ lens, const
     FrameMeta mnext = meta_of(tile + gridDim.x);
     __builtin_amdgcn_sched_barrier(0);
     int par = 0;
-    if constexpr (CACHED) {
+    if constexpr (INPLACE) {
+        // The decision pass: lookups and, in the intended use (every slot served or empty), no store.  One thread per FRAME of the
+        // workgroup's tiles, 16 tiles a round, so a frame's lookup chain (lens, clip_index -> cache_lens) is issued once and all of
+        // a round's are in flight together beside the first tile's samples.  Served frames and the frames of empty slots belong to
+        // their readers (clip_src.h); what is left to write before the transform are the zero rows behind a live clip's last
+        // frame: ragged clips drawn at another length than their cached one, 160 bytes per frame from the thread that found it.
+        // A workgroup without a live frame ends here, before the tables.
+        bool any_live = false;
+#pragma unroll 1
+        for (int t0 = blockIdx.x; t0 < ntiles; t0 += (NTHR / FT) * gridDim.x) {
+            const int tl = t0 + (tid / FT) * gridDim.x, frame = tid % FT;
+            if (tl < ntiles && tl * FT + frame < total_frames) {
+                const FrameMeta m = meta_at(tl, frame);
+                const FrameRef r = frame_of(m);
+                any_live |= r.live;
+                if (!r.live && r.cfr < 0 && !clip_empty(m.N)) {
+                    f32x4m* o = (f32x4m*)(out + ((size_t)tl * FT + frame) * NMFCC);          // 160-byte rows of a 16-byte-aligned buffer
+#pragma unroll
+                    for (int q = 0; q < NMFCC / 4; ++q) o[q] = f32x4m{0.f, 0.f, 0.f, 0.f};
+                }
+            }
+        }
+        if (__syncthreads_or(any_live) == 0) return;
+    } else if constexpr (CACHED) {
         // Every frame that is not live is written HERE, before any transform: a served frame is a copy of its row of the cache,
         // a dead one (the empty class, the rows behind a clip's last frame) zeros.  One thread per output element of the
         // workgroup's tiles, no barrier and no LDS in between, so the lookups (lens, clip_index -> cache_lens -> the row) of all
@@ -566,6 +598,7 @@ static int build_tables(var_ctx* c, bool psf, float** dev) {
     else {
         VAR_HIP_CHECK(c, hipFuncSetAttribute((const void*)mfcc_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, MFCC_LDS_BYTES));
         VAR_HIP_CHECK(c, hipFuncSetAttribute((const void*)mfcc_kernel<false, ClipCache>, hipFuncAttributeMaxDynamicSharedMemorySize, MFCC_LDS_BYTES));
+        VAR_HIP_CHECK(c, hipFuncSetAttribute((const void*)mfcc_kernel<false, ClipCacheInPlace>, hipFuncAttributeMaxDynamicSharedMemorySize, MFCC_LDS_BYTES));
     }
     return VAR_OK;
 }
@@ -593,13 +626,19 @@ int launch_mfcc_psf(var_ctx* c, hipStream_t s, const int16_t* pcm, const int* le
 }
 
 int launch_mfcc(var_ctx* c, hipStream_t s, const int16_t* pcm, const int* lens, const int* clip_index, int nclips,
-                int pcm_stride, int out_frames, float* out) {
+                int pcm_stride, int out_frames, float* out, bool in_place) {
     ProfScope prof(c, s, TAG_MFCC);
     // a bound clip cache serves this call when it was bound for this very pool and frame count; which SLOTS it serves is decided
     // on the device (lens and clip_index are device data, rewritten between the replays of a captured step)
     const auto& mc = c->mfcc_cache;
-    if (mc.feats && mc.pcm == pcm && mc.pcm_stride == pcm_stride && mc.out_frames == out_frames)
-        return launch_flavour<false>(c, s, pcm, lens, clip_index, nclips, pcm_stride, out_frames, c->mfcc_tab, out, "var_mfcc",
-                                     ClipCache{mc.lens, mc.feats, mc.rows});
+    if (mfcc_cache_matches(c, pcm, pcm_stride, out_frames)) {
+        const ClipCache cc{mc.lens, mc.feats, mc.rows};
+        if (in_place) {
+            if ((uintptr_t)out & 15) { VAR_SET_ERR(c, "var_mfcc: the in-place front-end needs a 16-byte-aligned feature buffer"); return VAR_ERR_ARG; }
+            return launch_flavour<false>(c, s, pcm, lens, clip_index, nclips, pcm_stride, out_frames, c->mfcc_tab, out, "var_mfcc",
+                                         ClipCacheInPlace{cc});
+        }
+        return launch_flavour<false>(c, s, pcm, lens, clip_index, nclips, pcm_stride, out_frames, c->mfcc_tab, out, "var_mfcc", cc);
+    }
     return launch_flavour<false>(c, s, pcm, lens, clip_index, nclips, pcm_stride, out_frames, c->mfcc_tab, out, "var_mfcc");
 }

@@ -12,6 +12,7 @@
 //         in registers while the workgroup walks its clips; one partial slab per workgroup, then a
 //         fixed-order reduction (bitwise reproducible, no float atomics).
 #include "var_common.h"
+#include "clip_src.h"
 
 namespace {
 constexpr int T0 = 100, F = 40, T1 = 48, T2 = 23, T3 = 11, T4 = 5;
@@ -100,7 +101,7 @@ __device__ __forceinline__ void snd_layer(const float* __restrict__ in, float* _
 }
 
 __global__ void __launch_bounds__(FNT)
-snd_fwd_kernel(const float* __restrict__ pos, const float* __restrict__ neg, int B, int clip_lo, int clip_hi,
+snd_fwd_kernel(const ClipSrc cs, int clip_lo, int clip_hi,
                const float* __restrict__ w0, const float* __restrict__ w1, const float* __restrict__ w2,
                const float* __restrict__ w3, const float* __restrict__ b0, const float* __restrict__ b1,
                const float* __restrict__ b2, const float* __restrict__ b3,
@@ -110,12 +111,14 @@ snd_fwd_kernel(const float* __restrict__ pos, const float* __restrict__ neg, int
     const int half = lane >> 5, l31 = lane & 31;
     const int clip0 = clip_lo + blockIdx.x * FNC;
     const int nclips = (clip_hi - clip0) < FNC ? (clip_hi - clip0) : FNC;
-#pragma unroll 1
+    // each clip's source once (clip_src.h), the four lookup chains in flight together; an empty slot and the clips behind the
+    // last one stage zeros without a load
+    const float* src[FNC];
+    clip_src_of_n<FNC>(cs, clip0, nclips, src);
+#pragma unroll
     for (int c = 0; c < FNC; ++c) {
-        const int clip = clip0 + c;
-        const bool valid = c < nclips;
-        const float* src = clip < B ? pos + (size_t)clip * T0 * F : neg + (size_t)(clip - B) * T0 * F;
-        stage_clip<FNT>(lds + F_XS + c * XCLIP, valid ? src : pos, valid, tid);
+        const bool valid = src[c] != nullptr;
+        stage_clip<FNT>(lds + F_XS + c * XCLIP, valid ? src[c] : w0, valid, tid);
     }
     __syncthreads();
     {   // layer 0: FNC x 48 (clip,t) pixels = FNW blocks of 32, one per wave; K = 200 = 5 blocks of 20 k-pairs
@@ -287,7 +290,13 @@ template <int NT>
 struct ClipRegs {
     static constexpr int N = (T0 * F / 4 + NT - 1) / NT;
     float4 v[N];
+    // src == nullptr (workgroup-uniform): an empty slot, zeros without a load
     __device__ __forceinline__ void load(const float* __restrict__ src, int tid) {
+        if (!src) {
+#pragma unroll
+            for (int i = 0; i < N; ++i) v[i] = float4{0.f, 0.f, 0.f, 0.f};
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < N; ++i) {
             const int e = tid + i * NT;
@@ -324,7 +333,7 @@ __device__ __forceinline__ void wgrad_taps(f32x16 (&acc)[3], float& bsum, const 
 }
 
 __global__ void __launch_bounds__(WNT)
-snd_wgrad_kernel(int clip_lo, int clip_hi, int B, const float* __restrict__ pos, const float* __restrict__ neg,
+snd_wgrad_kernel(int clip_lo, int clip_hi, const ClipSrc cs,
                  const float* __restrict__ a1, const float* __restrict__ a2, const float* __restrict__ a3,
                  const float* __restrict__ g1, const float* __restrict__ g2, const float* __restrict__ g3,
                  const float* __restrict__ g4, float* __restrict__ slabs) {
@@ -347,8 +356,7 @@ snd_wgrad_kernel(int clip_lo, int clip_hi, int B, const float* __restrict__ pos,
     RowRegs<T2, WNT> ry2, rg2;
     RowRegs<T3, WNT> ry3, rg3;
     RowRegs<T4, WNT> rg4;
-    auto load_clip = [&](int clip) {
-        const float* src = clip < B ? pos + (size_t)clip * T0 * F : neg + (size_t)(clip - B) * T0 * F;
+    auto load_clip = [&](int clip, const float* src) {
         rx.load(src, tid);
         ry1.load(a1 + (size_t)clip * 32 * T1, tid);
         ry2.load(a2 + (size_t)clip * 32 * T2, tid);
@@ -358,10 +366,32 @@ snd_wgrad_kernel(int clip_lo, int clip_hi, int B, const float* __restrict__ pos,
         rg3.load(g3 + (size_t)clip * 32 * T3, tid);
         rg4.load(g4 + (size_t)clip * 32 * T4, tid);
     };
-    if (clip_lo + (int)blockIdx.x < clip_hi) load_clip(clip_lo + blockIdx.x);
+    // One lookup chain per clip (clip_src.h), walked AHEAD of the clips so that load_clip never waits for it: entering the
+    // iteration of clip k the source of clip k + 1 is resolved and lens / clip_index of clip k + 2 are here; the iteration asks
+    // for the cached length of k + 2 and lens / clip_index of k + 3 at the head of its staging, whose LDS stores cover the round
+    // trip.  Every request is workgroup-uniform; slots past the end are clamped, their answers never used.
+    const int G = gridDim.x, cfirst = clip_lo + blockIdx.x;
+    const bool cached = cs.cache_feats != nullptr;
+    auto slot_of = [&](int clip) { return clip < clip_hi ? clip : clip_hi - 1; };
+    auto look12 = [&](int clip) {               // lens, clip_index
+        ClipLook k{0, 0, -1};
+        if (cached) { k.N = clip_len_of<true>(cs.lens, slot_of(clip)); k.row = clip_row_of<true>(cs.clip_index, slot_of(clip)); }
+        return k;
+    };
+    auto look3 = [&](const ClipLook& k) { return cached ? clip_cached_len<true>(cs.cache_lens, cs.cache_rows, k.row) : -1; };
+    const float* src_next = nullptr;            // source of clip + G
+    ClipLook k2 = look12(cfirst + 2 * G);       // lookups of clip + 2 G under way
+    if (cfirst < clip_hi) {
+        ClipLook k0 = look12(cfirst), k1 = look12(cfirst + G);
+        k0.clen = look3(k0); k1.clen = look3(k1);
+        load_clip(cfirst, clip_src_from(cs, cfirst, k0));
+        src_next = clip_src_from(cs, slot_of(cfirst + G), k1);
+    }
 #pragma unroll 1
-    for (int clip = clip_lo + blockIdx.x; clip < clip_hi; clip += gridDim.x) {
+    for (int clip = cfirst; clip < clip_hi; clip += G) {
         __syncthreads();                          // previous clip's MFMAs are done with the LDS images
+        k2.clen = look3(k2);                      // (behind the barrier, which waits for whatever is in flight in front of it)
+        const ClipLook k3 = look12(clip + 3 * G);
         rx.store(lds + W_X, tid);
         ry1.store<WY1S>(lds + W_Y1, tid);
         ry2.store<WY2S>(lds + W_Y2, tid);
@@ -371,7 +401,9 @@ snd_wgrad_kernel(int clip_lo, int clip_hi, int B, const float* __restrict__ pos,
         rg3.store<WG3S>(lds + W_G3, tid);
         rg4.store<WG4S>(lds + W_G4, tid);
         __syncthreads();
-        if (clip + (int)gridDim.x < clip_hi) load_clip(clip + gridDim.x);   // in flight during the MFMAs below
+        if (clip + G < clip_hi) load_clip(clip + G, src_next);   // in flight during the MFMAs below
+        src_next = clip_src_from(cs, slot_of(clip + 2 * G), k2);
+        k2 = k3;
         __builtin_amdgcn_sched_barrier(0);
         if (wave < 7) {
             const float* ap = lds + W_G1 + l31 * WG1S + half;
@@ -443,11 +475,21 @@ snd_reduce_kernel(const float* __restrict__ slabs, int G, float* __restrict__ ou
 static const int kSndG = 128;
 size_t snd_slab_floats() { return (size_t)kSndG * SND_SLICE; }
 
-int launch_snd_fwd(var_ctx* c, hipStream_t s, const float* params, const float* pos, const float* neg, int B) {
+// the kernels' clip geometry is fixed; a ClipSrc of another one, or whose two runs do not meet at B, is the library's own mistake
+static int check_clip_src(var_ctx* c, const ClipSrc& cs, int B) {
+    if (cs.frames != T0 || cs.split != B || (cs.cache_feats && (!cs.lens || !cs.cache_lens || cs.cache_rows <= 0))) {
+        VAR_SET_ERR(c, "sound CNN: clip source of %d frames, split %d at batch %d", cs.frames, cs.split, B);
+        return VAR_ERR_ARG;
+    }
+    return VAR_OK;
+}
+
+int launch_snd_fwd(var_ctx* c, hipStream_t s, const float* params, const ClipSrc& cs, int B) {
     const ParamLayout& L = c->pl;
     const PackLayout& K = c->kl;
-    const int lo = pos ? 0 : B, hi = neg ? 2 * B : B;
+    const int lo = cs.buf ? 0 : B, hi = cs.buf_hi ? 2 * B : B;
     if (hi <= lo) return VAR_OK;
+    { const int rc = check_clip_src(c, cs, B); if (rc != VAR_OK) return rc; }
     static unsigned attr_set = 0;      // bit d: set on device d (function attributes are per device)
     if (!(attr_set & var_dev_bit(c))) {
         VAR_HIP_CHECK(c, hipFuncSetAttribute((const void*)snd_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -455,7 +497,7 @@ int launch_snd_fwd(var_ctx* c, hipStream_t s, const float* params, const float* 
         attr_set |= var_dev_bit(c);
     }
     ProfScope prof(c, s, TAG_SND_FWD);
-    hipLaunchKernelGGL(snd_fwd_kernel, dim3((hi - lo + FNC - 1) / FNC), dim3(FNT), F_END * 4, s, pos, neg, B, lo, hi,
+    hipLaunchKernelGGL(snd_fwd_kernel, dim3((hi - lo + FNC - 1) / FNC), dim3(FNT), F_END * 4, s, cs, lo, hi,
                        c->wpack + K.snd_f[0], c->wpack + K.snd_f[1], c->wpack + K.snd_f[2], c->wpack + K.snd_f[3],
                        params + L.snd_b[0], params + L.snd_b[1], params + L.snd_b[2], params + L.snd_b[3],
                        c->sact[1], c->sact[2], c->sact[3], c->sact[4]);
@@ -467,7 +509,8 @@ int launch_snd_fwd(var_ctx* c, hipStream_t s, const float* params, const float* 
 int launch_snd_bwd(var_ctx* c, hipStream_t s, const float* params, float* grads, int B) {
     const ParamLayout& L = c->pl;
     const PackLayout& K = c->kl;
-    const int lo = c->saved_pos ? 0 : B, hi = c->saved_neg ? 2 * B : B;
+    const ClipSrc& cs = c->saved_src;          // the forward's sources: every backward of it reads the same rows
+    const int lo = cs.buf ? 0 : B, hi = cs.buf_hi ? 2 * B : B;
     if (hi <= lo) {
         { const int rz = var_zero_async(c, s, grads + L.snd_w[0], sizeof(float) * SND_SLICE); if (rz != VAR_OK) return rz; }
         return VAR_OK;
@@ -478,11 +521,12 @@ int launch_snd_bwd(var_ctx* c, hipStream_t s, const float* params, float* grads,
                            c->wpack + K.snd_d[1], c->wpack + K.snd_d[2], c->wpack + K.snd_d[3],
                            c->sact[1], c->sact[2], c->sact[3], c->gsact[4], c->gsact[3], c->gsact[2], c->gsact[1]);
     }
+    { const int rc = check_clip_src(c, cs, B); if (rc != VAR_OK) return rc; }
     const int G = hi - lo < kSndG ? hi - lo : kSndG;
     float* slabs = c->slabs + c->snd_slab_off;
     {
         ProfScope prof(c, s, TAG_SND_WGRAD);
-        hipLaunchKernelGGL(snd_wgrad_kernel, dim3(G), dim3(WNT), 0, s, lo, hi, B, c->saved_pos, c->saved_neg,
+        hipLaunchKernelGGL(snd_wgrad_kernel, dim3(G), dim3(WNT), 0, s, lo, hi, cs,
                            c->sact[1], c->sact[2], c->sact[3], c->gsact[1], c->gsact[2], c->gsact[3], c->gsact[4], slabs);
     }
     ProfScope prof(c, s, TAG_SND_REDUCE);

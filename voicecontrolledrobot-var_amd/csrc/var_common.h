@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "../../include/var_hip.h"
+#include "clip_src.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -198,6 +199,9 @@ struct var_ctx {
     long saved_bstride = 0;
     const float* saved_pos = nullptr;
     const float* saved_neg = nullptr;
+    // where the saved forward's sound CNN read each clip slot (clip_src.h): its backwards read the same rows, so the pool, the
+    // cache, lens and clip_index stay as they were until the last of them has run
+    ClipSrc saved_src = {nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0};
     const int* saved_index = nullptr;     // optional image gather index of the saved forward
     // side stream for the sound branch (runs beside the image branch) and its fork/join events
     int streams = 0;              // bit mask, see var_set_streams
@@ -366,7 +370,7 @@ int launch_img_bwd_chain(var_ctx* c, hipStream_t s, int B);   // img_chain.hip: 
 static constexpr int kTail2G = 256;   // persistent workgroups (= layer-0 and layer-1 slabs) of img_tail2_kernel: one image each
 int launch_img_bwd_tail2(var_ctx* c, hipStream_t s, int B);   // img_tail2.hip: wgrad 2 + dgrad 2 + wgrad 1 at 84 x 84
 int launch_img_bwd(var_ctx* c, hipStream_t s, const float* params, float* grads, int B);
-int launch_snd_fwd(var_ctx* c, hipStream_t s, const float* params, const float* pos, const float* neg, int B);
+int launch_snd_fwd(var_ctx* c, hipStream_t s, const float* params, const ClipSrc& cs, int B);
 int launch_snd_bwd(var_ctx* c, hipStream_t s, const float* params, float* grads, int B);
 int launch_heads_fwd(var_ctx* c, hipStream_t s, hipStream_t ss, const FwdPlan& p, const float* params, int B, bool has_img,
                      bool has_pos, bool has_neg, bool finish);
@@ -382,8 +386,15 @@ int launch_adam(var_ctx* c, hipStream_t s, float* p, const float* g, float* m, f
 int launch_adam_dev(var_ctx* c, hipStream_t s, float* p, const float* g, float* m, float* v, long n,
                     const float* lr_dev, float b1, float b2, float eps, float wd, int* step_dev, bool repack,
                     const int* idx_table, int row_ints, int n_rows, int* cursor, int* idx_row, int ahead_from);
+// in_place: under a bound cache that matches the call (mfcc_cache_matches) served and empty slots of `out` are left alone -- for
+// readers that resolve every slot through clip_src.h; without such a cache the flag changes nothing
 int launch_mfcc(var_ctx* c, hipStream_t s, const int16_t* pcm, const int* lens, const int* clip_index, int nclips,
-                int pcm_stride, int out_frames, float* out);
+                int pcm_stride, int out_frames, float* out, bool in_place = false);
+// the bound clip cache serves a front-end call over this pool and frame count
+static inline bool mfcc_cache_matches(const var_ctx* c, const int16_t* pcm, int pcm_stride, int out_frames) {
+    const auto& mc = c->mfcc_cache;
+    return mc.feats && mc.pcm == pcm && mc.pcm_stride == pcm_stride && mc.out_frames == out_frames;
+}
 
 // snd_bf16.hip: the iTHOR model's 11x5 sound convolution in its bf16 mode (patch staged in LDS, 32x32x16 bf16 MFMA)
 long snd_bf16_workspace_bytes(int nclips);
