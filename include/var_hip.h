@@ -629,7 +629,35 @@ int var_trunk_bwd(var_ctx* ctx, void* stream, int kind, const float* const* para
  * VAR_ERR_ARG, with a message that starts with the entry's name and nothing launched or written: kind not 0..2, B outside
  * 1..1024, a NULL pointer other than `saved` of the forward (a NULL entry of params included), image_bstride below C*H*W or a
  * batch of images of 4 GB or more, a workspace smaller than var_convstack_workspace_bytes, feat / saved / grads_flat /
- * workspace not 16-byte aligned.  The queries return VAR_ERR_ARG for a refused kind, index or B. */
+ * workspace not 16-byte aligned.  The queries return VAR_ERR_ARG for a refused kind, index or B.
+ *
+ * The _ex entries add `flags` and, for the backward, `d_saved`; the entries without _ex are the _ex entries called with
+ * flags = 0 and d_saved = NULL, and give the bits they always gave.
+ *   flags bit 0: bf16 operands, for kinds 0 and 1.  Every convolution product, in all three directions, multiplies operands
+ *       rounded to bf16 (round to nearest even) and accumulates in fp32; everything stored stays fp32 and every layout stays
+ *       as it is (feat, saved, grads_flat, their offsets, the parameter order).
+ *         forward, layer l   relu(conv(bf16(x_l), bf16(w_l)) + b_l): x_1 is the float image exactly as the fp32 path forms it
+ *                            from bytes, x_l the (pooled) fp32 map below; the bias is added in fp32, pools act on the stored
+ *                            fp32 maps.
+ *         data gradient      conv_transpose(bf16(g_l), bf16(w_l)), g_l the fp32 gradient wrt layer l's pre-activation (what
+ *                            the backward holds after the ReLU gate or the pool + ReLU backward).  Gates and pool routing are
+ *                            exact selections on fp32 values by the rules above.
+ *         weight gradient    the sum over pixels of bf16(g_l) * bf16(x_l); fp32 partial sums, slabs added in a fixed order
+ *                            that depends on the shape alone; stored, not accumulated.
+ *         bias gradient      fp32 channel sums of the unrounded g_l, as without the flag.
+ *       Kind 2 accepts the flag and computes in fp32, bit for bit as without it.  Parameters, gradients, Adam state, the
+ *       trunk, the head, the optimiser and the acting forwards are untouched by the mode.  Two sets of kernels serve it with
+ *       these semantics (csrc/convstack.hip): the gather-GEMM with its operands rounded on the way into
+ *       v_mfma_f32_32x32x16_bf16, and csrc/img_bf16.hip's kernels for the stride-1 padded layers behind conv 1 where they
+ *       have an instantiation of the shape (their filter tables are packed inside every call into the workspace).
+ *       Any other flag bit is refused.
+ *   d_saved (may be NULL): `saved`'s layout and offsets.  When given, the backward writes every layer's g_l there instead of
+ *       into its ping-pong workspace regions: g_l is the gated gradient with respect to the un-pooled map of convolution l,
+ *       the operand that layer's weight and data gradients consume.  In both precisions, for every kind; grads_flat has the
+ *       same bits with and without it.
+ *   var_convstack_workspace_bytes_ex   the workspace the _ex entries need at those flags (VAR_ERR_ARG for a refused flag bit).
+ * Refused like the rest (VAR_ERR_ARG, the entry's name first, nothing launched or written): a flag bit other than bit 0, a
+ * d_saved that is not 16-byte aligned, a workspace shorter than var_convstack_workspace_bytes_ex reports for those flags. */
 int var_convstack_n_params(int kind);
 long var_convstack_param_floats(int kind, int i);
 long var_convstack_grad_offset(int kind, int i);
@@ -642,6 +670,13 @@ int var_convstack_fwd(var_ctx* ctx, void* stream, int kind, const float* const* 
 int var_convstack_bwd(var_ctx* ctx, void* stream, int kind, const float* const* params, const void* image, int image_is_u8,
                       long image_bstride, int B, const float* saved, const float* d_feat, float* grads_flat, void* workspace,
                       long workspace_bytes);
+long var_convstack_workspace_bytes_ex(int kind, int B, int flags);
+int var_convstack_fwd_ex(var_ctx* ctx, void* stream, int kind, const float* const* params, const void* image, int image_is_u8,
+                         long image_bstride, int B, float* feat, float* saved /* may be NULL */, void* workspace,
+                         long workspace_bytes, int flags);
+int var_convstack_bwd_ex(var_ctx* ctx, void* stream, int kind, const float* const* params, const void* image, int image_is_u8,
+                         long image_bstride, int B, const float* saved, const float* d_feat, float* grads_flat, void* workspace,
+                         long workspace_bytes, float* d_saved /* may be NULL */, int flags);
 
 /* The frozen iTHOR encoder's reward step at RL batch sizes -----------------------------------------------------------
  * What the vectorised-env wrapper asks of the frozen pretext model on every environment step

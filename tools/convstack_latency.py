@@ -7,9 +7,16 @@ under PyTorch autograd) against bind_convs (stacks in HIP).  One process, both l
 outside the timed part), the legs alternating; medians over the runs, three repeats, spread reported.  Host wall clock around
 work that ends in a device synchronise.  Writes profiles/convstack_latency.json.
 
+--bf16 adds a third leg beside the two, conv_stack_eval(precision="bf16") / bind_convs(policy, precision="bf16"), alternated with
+them in the same process (the yardstick is the fp32 conv_stack_eval leg), and then records the mode's effect on PPO at (T, N) =
+(100, 4) for both policies with tests/convstack_cpu.policy_params weights: |ratio - 1| of the importance ratio when the old
+log-probabilities come from the fp32 evaluation (which stands for the fp32 acting forward) and the new ones from the bf16
+evaluation, and each gradient array's distance from the fp32 leg's.  Writes profiles/convstack_bf16_latency.json.
+
 usage: python tools/convstack_latency.py [--runs 30] [--repeats 3] [--out profiles/convstack_latency.json] [--only-hip]
-           [--configs 0:400,...]
-(--only-hip runs the new op alone, three iterations per shape: the run to put under rocprofv3 --kernel-trace --stats)"""
+           [--configs 0:400,...] [--bf16]
+(--only-hip runs the new op alone, three iterations per shape: the run to put under rocprofv3 --kernel-trace --stats; with --bf16
+it runs the bf16 leg alone)"""
 import argparse
 import json
 import os
@@ -75,14 +82,71 @@ def agreement(names, ga, gb):
     return {"max_rel_difference": worst[0], "array": worst[1]}
 
 
+def ppo_effect(kind, seed=9):
+    """What bf16 evaluation does to the first minibatch after a rollout at (T, N) = (100, 4): max and mean |ratio - 1| with the old
+    log-probabilities from the fp32 evaluation of the same minibatch, and every gradient array's distance from the fp32 leg's
+    (largest absolute difference over the fp32 array's largest magnitude).  Weights: tests/convstack_cpu.policy_params."""
+    from tests import convstack_cpu as cc
+    from tests import trunk_cpu as tc
+    n_act = 8 if kind else 2
+    Q = cc.policy_params(kind, seed, n_act)
+    pol = tc.drop_in_policy(kind, 0).to("cuda")
+    with torch.no_grad():
+        for k, v in pol.named_parameters():
+            v.copy_(torch.from_numpy(Q[k]).cuda())
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    M = T * N
+    rn = lambda *s: torch.randn(*s, device="cuda", generator=g)   # noqa: E731
+    obs = {"image": torch.randint(0, 256, (M, 3, 96, 96), device="cuda", generator=g, dtype=torch.uint8), "image_feat": rn(M, 3),
+           "goal_sound_feat": rn(M, 3)}
+    if kind:
+        obs["occupancy"] = (torch.rand(M, 1, 9, 9, device="cuda", generator=g) < 0.3).to(torch.uint8) * 255
+    else:
+        obs["robot_pose"] = rn(M, 2)
+    masks = torch.ones(T, N, device="cuda")
+    masks[0] = 0.0
+    hxs = 0.5 * rn(N, tc.hidden(kind))
+    logp, actions = {}, None
+    with torch.no_grad():
+        for prec in ("fp32", "bf16"):
+            var_amd.bind_convs(pol, precision=prec)
+            _value, feats, _h, _ = pol.base(obs, hxs, masks.view(M, 1), infer=False)
+            if kind:                                               # Categorical over the logits / DiagGaussian (models/ppo/distributions.py)
+                lsm = torch.log_softmax(pol.dist.linear(feats), dim=-1)
+                if actions is None:
+                    actions = torch.multinomial(lsm.exp(), 1, generator=g)
+                logp[prec] = lsm.gather(1, actions)
+            else:
+                mean, logstd = pol.dist.fc_mean(feats), pol.dist.logstd._bias.view(1, -1)
+                if actions is None:
+                    actions = mean + logstd.exp() * rn(M, n_act)
+                logp[prec] = (-0.5 * ((actions - mean) / logstd.exp()) ** 2 - logstd - 0.9189385332046727).sum(-1, keepdim=True)
+    ratio = torch.exp(logp["bf16"] - logp["fp32"])
+    sample = (obs, hxs, actions, rn(M, 1), rn(M, 1), masks.view(M, 1), logp["fp32"], rn(M, 1))
+    agent = var_amd.PPO(pol, 0.2, 1, 1, 0.5, 0.01, lr=1e-4, eps=1e-5, max_grad_norm=0.5)
+    grads = {}
+    for prec in ("fp32", "bf16"):
+        var_amd.bind_convs(pol, precision=prec)
+        agent.optimizer.zero_grad()
+        agent.loss(sample)[0].backward()
+        grads[prec] = {n: p.grad.clone() for n, p in pol.named_parameters()}
+    dist_g = {n: float((grads["bf16"][n] - v).abs().max() / v.abs().max()) for n, v in grads["fp32"].items()}
+    return {"what": "effect of bf16 evaluation on the first PPO minibatch after a rollout", "kind": kind, "T": T, "N": N,
+            "max_abs_ratio_minus_1": float((ratio - 1).abs().max()), "mean_abs_ratio_minus_1": float((ratio - 1).abs().mean()),
+            "gradient_distance_from_fp32": dist_g, "largest_gradient_distance": max(dist_g.values())}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=30)
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "convstack_latency.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--bf16", action="store_true")
     ap.add_argument("--only-hip", action="store_true")
     ap.add_argument("--configs", default=",".join(f"{k}:{b}" for k, b in CONFIGS), help="kind:B,... (default: all)")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "convstack_bf16_latency.json" if a.bf16 else "convstack_latency.json")
     assert torch.cuda.is_available(), "needs a GPU"
     pols = {0: make_policy(0), 1: make_policy(1)}
     g = torch.Generator(device="cuda").manual_seed(1)
@@ -104,17 +168,26 @@ def main():
         def torch_autograd():
             return torch.autograd.grad((torch_module(image.float() / 255.0) * d_feat).sum(), params)
 
+        def hip_bf16():
+            return torch.autograd.grad((var_amd.conv_stack_eval(module, image, precision="bf16") * d_feat).sum(), params)
+
         if a.only_hip:
             for _ in range(3):
-                hip()
+                (hip_bf16 if a.bf16 else hip)()
             torch.cuda.synchronize()
             continue
         names = var_amd.convstack.stack_param_names(kind)
         agree = agreement(names, hip(), torch_autograd())
-        meds = measure({"hip": hip, "torch": torch_autograd}, a.runs, a.repeats)
+        legs = {"hip": hip, "torch": torch_autograd}
+        if a.bf16:
+            legs["hip_bf16"] = hip_bf16
+        meds = measure(legs, a.runs, a.repeats)
         row = summarise({"what": "conv_stack_eval forward + backward", "kind": kind, "B": B, "gradient_agreement": agree,
                          "forward_gflop": 2e-9 * MACS[kind] * B}, meds)
         row["ratio_torch_over_hip"] = row["torch_us"] / row["hip_us"]
+        if a.bf16:
+            row["bf16_gradient_distance_from_fp32"] = agreement(names, hip_bf16(), hip())
+            row["ratio_hip_over_hip_bf16"] = row["hip_us"] / row["hip_bf16_us"]
         print(json.dumps(row), flush=True)
         rows.append(row)
     if a.only_hip:
@@ -129,6 +202,8 @@ def main():
     sample = (obs, 0.5 * rn(N, 512), rn(M, 2), rn(M, 1), rn(M, 1), masks.view(M, 1), rn(M, 1) - 2.0, rn(M, 1))
     agent = var_amd.PPO(pol, 0.2, 1, 1, 0.5, 0.01, lr=1e-4, eps=1e-5, max_grad_norm=0.5)
     binders = {"bind_convs": var_amd.bind_convs, "bind_trunk": var_amd.bind_trunk}
+    if a.bf16:
+        binders["bind_convs_bf16"] = lambda p: var_amd.bind_convs(p, precision="bf16")
 
     def leg(name):
         def fn():
@@ -146,8 +221,15 @@ def main():
     meds = measure(legs, a.runs, a.repeats)
     row = summarise({"what": "PPO.loss(sample)[0].backward(), arm_VAR", "T": T, "N": N, "gradient_agreement": agree}, meds)
     row["ratio_bind_trunk_over_bind_convs"] = row["bind_trunk_us"] / row["bind_convs_us"]
+    if a.bf16:
+        row["ratio_bind_convs_over_bind_convs_bf16"] = row["bind_convs_us"] / row["bind_convs_bf16_us"]
     print(json.dumps(row), flush=True)
     rows.append(row)
+    if a.bf16:
+        for kind in (0, 1):
+            row = ppo_effect(kind)
+            print(json.dumps(row), flush=True)
+            rows.append(row)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump({"what": "microseconds per call (host wall clock around work that ends in a device synchronise), medians of `runs` "

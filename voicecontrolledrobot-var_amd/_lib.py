@@ -113,6 +113,9 @@ _SIGNATURES = {
     "var_convstack_workspace_bytes": (_l, [_i, _i]),
     "var_convstack_fwd": (_i, [_vp, _vp, _i, _vp, _vp, _i, _l, _i, _vp, _vp, _vp, _l]),
     "var_convstack_bwd": (_i, [_vp, _vp, _i, _vp, _vp, _i, _l, _i, _vp, _vp, _vp, _vp, _l]),
+    "var_convstack_workspace_bytes_ex": (_l, [_i, _i, _i]),
+    "var_convstack_fwd_ex": (_i, [_vp, _vp, _i, _vp, _vp, _i, _l, _i, _vp, _vp, _vp, _l, _i]),
+    "var_convstack_bwd_ex": (_i, [_vp, _vp, _i, _vp, _vp, _i, _l, _i, _vp, _vp, _vp, _vp, _l, _vp, _i]),
     "var_ithor_reward_plan": (_i, [_vp, _i, _i]),
     "var_ithor_reward_pack": (_i, [_vp, _vp, _vp]),
     "var_ithor_reward_step": (_i, [_vp, _vp, _vp, _vp, _i, _l, _vp, _i, _vp, _vp, _vp]),

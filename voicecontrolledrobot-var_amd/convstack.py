@@ -5,11 +5,17 @@ autograd node.
 
     feat = conv_stack_eval(base.imgCNN, image)           # (B, 1152); image uint8 (divided by 255 on the device) or float32
     ppo = PPO(bind_convs(policy), ...)                   # policy.base(obs, hxs, masks): conv_stack_eval, then trunk_eval
+    ppo = PPO(bind_convs(policy, precision="bf16"), ...) # the same with the stacks' products on bf16 operands
+
+precision="bf16" (flags bit 0 of var_convstack_fwd_ex / _bwd_ex; include/var_hip.h has the definition): every convolution product
+of kinds 0 and 1, in all three directions, multiplies operands rounded to bf16 and accumulates in fp32; everything stored, every
+layout, the parameters, their gradients, the trunk, the optimiser and the acting forwards stay fp32.  Kind 2 computes in fp32
+under either name.  Opt-in: without it every entry gives the bits it gave before the mode existed.
 
 bind_convs works on the reference's Policy and on ArmNetPolicy / IthorNetPolicy alike; with it the whole base is evaluated, forward
 and backward, without a PyTorch autograd kernel and without MIOpen (PPO(..., fused_optimizer=True) takes the gradient clip and
 Adam from PyTorch's kernels as well: optim.py).  The op differentiates in the parameters only: the
-observations carry no gradient in PPO.  GPU only, fp32 only: there is no CPU fallback, anything else raises VarHipError before a
+observations carry no gradient in PPO.  GPU only, fp32 tensors only: there is no CPU fallback, anything else raises VarHipError before a
 launch.  Nothing here reads the device, so the op can sit inside a torch.cuda.graph capture."""
 import ctypes
 import types
@@ -30,6 +36,13 @@ _STACKS = {
     2: ((1, 9, 9), ((1, 64, 2, 1, False), (64, 32, 2, 1, False))),
 }
 MAX_BATCH = 1024
+PRECISIONS = {"fp32": 0, "bf16": 1}                      # name -> flags of the _ex entries
+
+
+def _flags(precision, who):
+    if precision not in PRECISIONS:
+        raise VarHipError(f"{who}: precision {precision!r} is neither 'fp32' nor 'bf16'")
+    return PRECISIONS[precision]
 
 
 def _pair(v):
@@ -150,16 +163,16 @@ def _pointer_table(tensors):
     return (ctypes.c_void_p * len(tensors))(*(t.data_ptr() for t in tensors))
 
 
-def _workspace(c, kind, B, dev):
-    nbytes = c.lib.var_convstack_workspace_bytes(kind, B)
+def _workspace(c, kind, B, dev, flags):
+    nbytes = c.lib.var_convstack_workspace_bytes_ex(kind, B, flags)
     if nbytes < 0:
-        raise VarHipError(f"var_convstack_workspace_bytes refused kind {kind}, B {B}")
+        raise VarHipError(f"var_convstack_workspace_bytes_ex refused kind {kind}, B {B}, flags {flags}")
     return torch.empty(int(nbytes), dtype=torch.uint8, device=dev), int(nbytes)
 
 
 class _ConvStack(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, kind, keep, image, *params):
+    def forward(ctx, kind, keep, flags, grad_maps, image, *params):
         B, nfeat = _check(kind, image, params)
         dev = image.device
         img = image.detach().contiguous()
@@ -169,14 +182,21 @@ class _ConvStack(torch.autograd.Function):
         feat = new(B, nfeat)
         need = keep or any(ctx.needs_input_grad)
         saved = new(c.lib.var_convstack_saved_floats(kind, B)) if need else None
-        ws, nbytes = _workspace(c, kind, B, dev)
+        if grad_maps is not None:
+            n = c.lib.var_convstack_saved_floats(kind, B)
+            if (not torch.is_tensor(grad_maps) or grad_maps.dtype != torch.float32 or grad_maps.device != dev or grad_maps.dim() != 1
+                    or grad_maps.numel() != n or not grad_maps.is_contiguous() or grad_maps.requires_grad):
+                raise VarHipError(f"conv_stack_eval: grad_maps must be a contiguous float32 tensor of {n} elements (saved's length) on "
+                                  f"{dev} that requires no grad")
+        ws, nbytes = _workspace(c, kind, B, dev, flags)
         u8 = int(img.dtype == torch.uint8)
-        c.check(c.lib.var_convstack_fwd(c.handle, current_stream_handle(), kind, _pointer_table(ps), ptr(img), u8, img.stride(0), B,
-                                        ptr(feat), ptr(saved), ptr(ws), nbytes),
-                "var_convstack_fwd")
+        c.check(c.lib.var_convstack_fwd_ex(c.handle, current_stream_handle(), kind, _pointer_table(ps), ptr(img), u8, img.stride(0), B,
+                                           ptr(feat), ptr(saved), ptr(ws), nbytes, flags),
+                "var_convstack_fwd_ex")
         if need:
             ctx.save_for_backward(img, saved, *ps)
-        ctx.dims = (kind, B, u8)
+        ctx.dims = (kind, B, u8, flags)
+        ctx.grad_maps = grad_maps
         ctx.set_materialize_grads(False)
         if keep:
             ctx.mark_non_differentiable(saved)
@@ -186,10 +206,10 @@ class _ConvStack(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, d_feat, *_):
-        kind, B, u8 = ctx.dims
+        kind, B, u8, flags = ctx.dims
         img, saved, *ps = ctx.saved_tensors
         if d_feat is None:
-            return (None, None, None) + (None,) * len(ps)
+            return (None,) * (5 + len(ps))
         dev = img.device
         d_feat = d_feat.contiguous()
         c = Context.get(dev.index)
@@ -197,23 +217,28 @@ class _ConvStack(torch.autograd.Function):
         n = len(ps)
         offs = [lib.var_convstack_grad_offset(kind, i) for i in range(n + 1)]
         flat = torch.empty(offs[n], dtype=torch.float32, device=dev)
-        ws, nbytes = _workspace(c, kind, B, dev)
-        c.check(lib.var_convstack_bwd(c.handle, current_stream_handle(), kind, _pointer_table(ps), ptr(img), u8, img.stride(0), B,
-                                      ptr(saved), ptr(d_feat), ptr(flat), ptr(ws), nbytes),
-                "var_convstack_bwd")
+        ws, nbytes = _workspace(c, kind, B, dev, flags)
+        c.check(lib.var_convstack_bwd_ex(c.handle, current_stream_handle(), kind, _pointer_table(ps), ptr(img), u8, img.stride(0), B,
+                                         ptr(saved), ptr(d_feat), ptr(flat), ptr(ws), nbytes, ptr(ctx.grad_maps), flags),
+                "var_convstack_bwd_ex")
         grads = tuple(flat[offs[i]:offs[i] + p.numel()].view(p.shape) for i, p in enumerate(ps))   # views of the one buffer
-        return (None, None, None) + grads
+        return (None,) * 5 + grads
 
 
-def conv_stack_eval(module, image, return_saved=False):
+def conv_stack_eval(module, image, return_saved=False, precision="fp32", grad_maps=None):
     """module: armNet_VAR.imgCNN (96 x 96 branch), ai2thorNet_VAR.imgCNN or occupancyCNNMLP (its two convolutions are evaluated,
     the Linear layers behind its Flatten belong to trunk_eval); image (B, 3, 96, 96) | (B, 1, 9, 9), uint8 (divided by 255 on the
     device) or float32 -> feat (B, 1152 | 288), the last map flattened.  Differentiable in the module's convolution parameters
     (their gradients are views of one flat buffer), not in the image.  return_saved: also (saved, map) -- the flat tensor of
-    saved activations and saved_map's name -> (offset, shape)."""
+    saved activations and saved_map's name -> (offset, shape).  precision: "fp32", or "bf16" for products on operands rounded
+    to bf16 (the module docstring; kind 2 computes in fp32 either way); anything else raises VarHipError before the device is
+    touched.  grad_maps: a float32 CUDA tensor of `saved`'s length and layout that the backward fills with every convolution's
+    gated gradient map g_l (the gradient with respect to its un-pooled pre-activation), in either precision; the parameter
+    gradients have the same bits with and without it."""
+    flags = _flags(precision, "conv_stack_eval")
     kind = stack_kind(module)
     params = stack_parameters(module, kind)
-    out = _ConvStack.apply(kind, bool(return_saved), image, *params)
+    out = _ConvStack.apply(kind, bool(return_saved), flags, grad_maps, image, *params)
     if return_saved:
         return out[0], out[1], saved_map(kind, image.shape[0])
     return out
@@ -231,17 +256,19 @@ def _convs_forward(self, inputs, rnn_hxs, masks, **kw):
         occ = None
     else:
         motor_in = inputs['image_feat'].float()
-        occ = conv_stack_eval(self.occupancyCNNMLP, _as_image(inputs['occupancy']))
-    feat = conv_stack_eval(self.imgCNN, _as_image(inputs['image']))
+        occ = conv_stack_eval(self.occupancyCNNMLP, _as_image(inputs['occupancy']), precision=self._convs_precision)
+    feat = conv_stack_eval(self.imgCNN, _as_image(inputs['image']), precision=self._convs_precision)
     value, feats, h_T = trunk_eval(self, feat, motor_in, inputs['goal_sound_feat'].float(), rnn_hxs, masks, occ=occ)
     return value, feats, h_T, {}
 
 
-def bind_convs(policy):
+def bind_convs(policy, precision="fp32"):
     """Give policy.base (the reference's Policy, ArmNetPolicy, IthorNetPolicy) a forward(inputs, rnn_hxs, masks, **kw) -> (value,
     actor_features, rnn_hxs, {}) that runs imgCNN (and, for ai2thor_VAR, occupancyCNNMLP's two convolutions) through
     conv_stack_eval and everything behind them through trunk_eval; returns the policy, so that PPO(bind_convs(policy), ...) reads
-    like bind_trunk."""
+    like bind_trunk.  precision: conv_stack_eval's, for the stacks alone -- the trunk, the head, the parameters, their gradients and
+    the acting forwards stay fp32, so with "bf16" the importance ratio of the first minibatch after a rollout is close to 1, not 1."""
+    _flags(precision, "bind_convs")
     base = getattr(policy, "base", None)
     if base is None:
         raise VarHipError("bind_convs: the policy has no .base")
@@ -256,5 +283,6 @@ def bind_convs(policy):
         if stack_kind(base.occupancyCNNMLP) != 2:
             raise VarHipError("bind_convs: occupancyCNNMLP does not start with the reference's two convolutions")
         stack_parameters(base.occupancyCNNMLP, 2)
+    base._convs_precision = precision
     base.forward = types.MethodType(_convs_forward, base)
     return policy

@@ -13,12 +13,26 @@
 //                       saved: the backward pools the saved un-pooled map again (a function of that map alone).
 // Kernel boundaries order the layers: no atomics, no spin-wait, no grid barrier.  Every split is a function of the shape alone,
 // nothing packed outlives a call, equal inputs give equal bits.  Nothing reads the device.
+//
+// bf16 mode (flags bit 0 of the _ex entries; kinds 0 and 1, kind 2 computes in fp32 whatever the flag): every convolution product,
+// in all three directions, multiplies operands rounded to bf16 (round to nearest even) and accumulates in fp32.  Everything stored
+// stays fp32 and every layout stays as it is.  Forward: relu(conv(bf16(x_l), bf16(w_l)) + b_l), the bias added in fp32, x_1 the
+// float image as the fp32 path forms it from bytes, pools on the stored fp32 maps.  Data gradient: conv_transpose(bf16(g_l),
+// bf16(w_l)), g_l the fp32 gradient wrt layer l's pre-activation; gates and pool routing are exact selections on fp32 values.
+// Weight gradient: the sum over pixels of bf16(g_l) * bf16(x_l), fp32 partial sums, slabs added in an order that depends on the
+// shape alone, stored.  Bias gradient: fp32 channel sums of the unrounded g_l.  Two tiers serve it, with these semantics both:
+//   tier 1  the gather-GEMM with BF = true (gg.h rounds both operands on their way from its fp32 LDS tile into
+//           v_mfma_f32_32x32x16_bf16): conv 1, the stride-2 and unpadded layers, every weight gradient tier 2 does not cover
+//   tier 2  img_bf16.hip's c3_kernel (forward and data gradient) and c3w_kernel (weight gradient) for the stride-1 padded layers
+//           behind conv 1, where it has an instantiation of the shape; its fragment table is packed inside every call into the
+//           caller's workspace
 #include "gg.h"
 
 namespace {
 
 constexpr int kMaxConvs = 8;
 constexpr int kMaxBatch = 1024;
+constexpr int kFlagBf16 = 1;       // flags bit 0 of the _ex entries
 // geometry ids of the 3 x 3 filters the stacks use
 enum { G_S1P1 = 0, G_S2P0 = 1, G_S1P0 = 2, G_S2P1 = 3 };
 typedef Geo<3, 3, 1, 1, 1, 1> GeoS1P1;
@@ -91,9 +105,18 @@ inline int wgrad_split(const Stack& st, const Shapes& sh, int l, long B) {
 }
 
 // the workspace, in floats from its start (every region a multiple of 4 floats long)
-struct Layout { long pooled, ga, gb, gp, slab, bpart, acts, total; };
+struct Layout { long pooled, ga, gb, gp, slab, bpart, tab, acts, total; };
 inline long up4(long n) { return (n + 3) & ~3L; }
-inline Layout layout_of(const Stack& st, long B) {
+// bf16 mode: whether layer l is one of the stride-1 padded layers behind conv 1 (tier 2's candidates)
+// (-DVAR_CONVSTACK_TIER1: a tuning build that serves every layer from tier 1, to time the tiers against each other)
+inline bool t2_candidate(const Stack& st, int l) {
+#ifdef VAR_CONVSTACK_TIER1
+    return false;
+#else
+    return !st.small && l > 0 && st.L[l].geo == G_S1P1;
+#endif
+}
+inline Layout layout_of(const Stack& st, long B, bool bf = false) {
     const Shapes sh = shapes_of(st);
     long max_act = 0, max_pool = 0, max_slab = 0;
     for (int l = 0; l < st.n; ++l) {
@@ -102,6 +125,10 @@ inline Layout layout_of(const Stack& st, long B) {
         if (st.L[l].pool && a / 4 > max_pool) max_pool = a / 4;
         const long s = (long)wgrad_split(st, sh, l, B) * st.L[l].cin * 9 * st.L[l].cout;
         if (s > max_slab) max_slab = s;
+        if (bf && t2_candidate(st, l)) {
+            const long s2 = img_bf16_wgrad_slab_floats(st.L[l].cin, st.L[l].cout, sh.hout[l], (int)B);
+            if (s2 > max_slab) max_slab = s2;
+        }
     }
     Layout y{};
     long o = 0;
@@ -112,6 +139,7 @@ inline Layout layout_of(const Stack& st, long B) {
     y.gp = o; o += up4(max_pool);
     y.slab = o; o += up4(max_slab);
     y.bpart = o; o += kChanChunks * 256;
+    y.tab = o; if (bf && !st.small) o += up4(img_bf16_table_bytes() / 4);      // tier 2's fragment table, packed inside every call
     y.acts = fwd_base;                                   // a forward without `saved` keeps its activations here
     const long fwd = fwd_base + up4(saved_offset(st, B, st.n));
     y.total = o > fwd ? o : fwd;
@@ -310,14 +338,14 @@ struct WgradSlabP : ConvWgradP<G, U8, false> {
 #define CS_CHECK(c) VAR_HIP_CHECK(c, hipGetLastError())
 inline dim3 g1(long n) { return dim3((unsigned)((n + 255) / 256)); }
 
-template <class G, bool U8>
+template <class G, bool U8, bool BF>
 int conv_fwd(var_ctx* c, hipStream_t s, const ConvDims& d, const void* x, const float* w, const float* bias, float* y) {
     ConvFwdP<G, U8, false> p{};
     p.M = d.B * d.HO * d.WO; p.N = d.COUT; p.K = d.CIN * G::KHW; p.nsplit = 1;
     p.d = d; p.x = x; p.w = w; p.bias = bias; p.y = y;
-    return gg_launch(c, s, p);
+    return gg_launch<ConvFwdP<G, U8, false>, GG_KC, BF>(c, s, p);
 }
-template <class G>
+template <class G, bool BF>
 int conv_dgrad(var_ctx* c, hipStream_t s, const ConvDims& d, const float* gy, const float* w, float* dx, const float* mask) {
     if constexpr (G::SH == 2) {
         typedef ConvDgradS2P<G, false> P;
@@ -326,20 +354,20 @@ int conv_dgrad(var_ctx* c, hipStream_t s, const ConvDims& d, const float* gy, co
         p.inv_h2w2 = 1.f / (float)(p.H2 * p.W2); p.inv_w2 = 1.f / (float)p.W2;
         p.M = d.B * p.H2 * p.W2; p.N = d.CIN; p.K = d.COUT * P::NKY * P::NKX; p.nsplit = 1;
         p.d = d; p.gy = gy; p.w = w; p.dx = dx; p.mask = mask;
-        return gg_launch(c, s, p, 4);
+        return gg_launch<P, GG_KC, BF>(c, s, p, 4);
     } else {
         ConvDgradP<G> p{};
         p.M = d.B * d.H * d.W; p.N = d.CIN; p.K = d.COUT * G::KHW; p.nsplit = 1;
         p.d = d; p.gy = gy; p.w = w; p.dx = dx; p.mask = mask;
-        return gg_launch(c, s, p);
+        return gg_launch<ConvDgradP<G>, GG_KC, BF>(c, s, p);
     }
 }
-template <class G, bool U8>
+template <class G, bool U8, bool BF>
 int conv_wgrad(var_ctx* c, hipStream_t s, const ConvDims& d, const void* x, const float* gy, float* slab, int nsplit) {
     WgradSlabP<G, U8> p{};
     p.M = d.CIN * G::KHW; p.N = d.COUT; p.K = d.B * d.HO * d.WO; p.nsplit = nsplit;
     p.d = d; p.x = x; p.gy = gy; p.dw = nullptr; p.slab = slab;
-    return gg_launch<WgradSlabP<G, U8>, kWgradKC>(c, s, p);
+    return gg_launch<WgradSlabP<G, U8>, kWgradKC, BF>(c, s, p);
 }
 
 int fold(var_ctx* c, hipStream_t s, float* out, const float* slabs, int n, int nsplit, long stride) {
@@ -370,13 +398,17 @@ int small_wgrad(var_ctx* c, hipStream_t s, const SmallConv& d, bool u8, const vo
 }
 
 // only the first layer of a stack can read bytes
-#define CS_GEO(geo, u8, CALL_U8, CALL)                                     \
+#define CS_GEO1(geo, u8, CALL_U8, CALL)                                    \
     switch (geo) {                                                          \
         case G_S1P1: { typedef GeoS1P1 G; if (u8) { CALL_U8; } else { CALL; } break; } \
         case G_S2P1: { typedef GeoS2P1 G; if (u8) { CALL_U8; } else { CALL; } break; } \
         case G_S2P0: { typedef GeoS2P0 G; CALL; break; }                   \
         default: { typedef GeoS1P0 G; CALL; break; }                       \
     }
+// the calls name BF: the operands rounded to bf16 (tier 1 of the bf16 mode) or not
+#define CS_GEO(geo, u8, bf, CALL_U8, CALL)                                 \
+    if (bf) { constexpr bool BF = true; CS_GEO1(geo, u8, CALL_U8, CALL) }  \
+    else { constexpr bool BF = false; CS_GEO1(geo, u8, CALL_U8, CALL) }
 
 inline ConvDims dims_of(const Stack& st, const Shapes& sh, int l, int B, long xb) {
     const int g = st.L[l].geo;
@@ -389,7 +421,8 @@ inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // the checks both entries share; NULL when the call is accepted
 const char* common_error(int kind, const float* const* params, const void* image, int is_u8, long image_bstride, int B,
-                         const void* ws, long ws_bytes, char* buf, size_t nbuf) {
+                         const void* ws, long ws_bytes, int flags, char* buf, size_t nbuf) {
+    if (flags & ~kFlagBf16) { snprintf(buf, nbuf, "flags = %d: bit 0 (bf16 operands) is the only one", flags); return buf; }
     if (!kind_ok(kind)) { snprintf(buf, nbuf, "kind %d is none of 0 (arm_VAR imgCNN), 1 (ai2thor_VAR imgCNN), 2 (occupancy convolutions)", kind); return buf; }
     if (B < 1 || B > kMaxBatch) { snprintf(buf, nbuf, "B = %d is outside 1..%d", B, kMaxBatch); return buf; }
     const Stack& st = kStacks[kind];
@@ -402,8 +435,11 @@ const char* common_error(int kind, const float* const* params, const void* image
         snprintf(buf, nbuf, "image_bstride %ld: at least %ld elements, and the whole batch below 4 GB", image_bstride, per);
         return buf;
     }
-    const long need = 4 * layout_of(st, B).total;
-    if (ws_bytes < need) { snprintf(buf, nbuf, "workspace of %ld bytes, %ld needed (var_convstack_workspace_bytes)", ws_bytes, need); return buf; }
+    const long need = 4 * layout_of(st, B, flags & kFlagBf16).total;
+    if (ws_bytes < need) {
+        snprintf(buf, nbuf, "workspace of %ld bytes, %ld needed (var_convstack_workspace_bytes_ex at flags %d)", ws_bytes, need, flags);
+        return buf;
+    }
     return nullptr;
 }
 
@@ -426,29 +462,32 @@ extern "C" long var_convstack_saved_floats(int kind, int B) {
     if (!kind_ok(kind) || B < 1 || B > kMaxBatch) return VAR_ERR_ARG;
     return saved_offset(kStacks[kind], B, kStacks[kind].n);
 }
-extern "C" long var_convstack_workspace_bytes(int kind, int B) {
-    if (!kind_ok(kind) || B < 1 || B > kMaxBatch) return VAR_ERR_ARG;
-    return 4 * layout_of(kStacks[kind], B).total;
+extern "C" long var_convstack_workspace_bytes_ex(int kind, int B, int flags) {
+    if (!kind_ok(kind) || B < 1 || B > kMaxBatch || (flags & ~kFlagBf16)) return VAR_ERR_ARG;
+    return 4 * layout_of(kStacks[kind], B, flags & kFlagBf16).total;
 }
+extern "C" long var_convstack_workspace_bytes(int kind, int B) { return var_convstack_workspace_bytes_ex(kind, B, 0); }
 
-extern "C" int var_convstack_fwd(var_ctx* c, void* stream, int kind, const float* const* params, const void* image, int image_is_u8,
-                                 long image_bstride, int B, float* feat, float* saved, void* workspace, long workspace_bytes) {
+namespace {
+int fwd_impl(const char* entry, var_ctx* c, void* stream, int kind, const float* const* params, const void* image, int image_is_u8,
+             long image_bstride, int B, float* feat, float* saved, void* workspace, long workspace_bytes, int flags) {
     if (!c) return VAR_ERR_ARG;
     char why[256];
-    if (common_error(kind, params, image, image_is_u8, image_bstride, B, workspace, workspace_bytes, why, sizeof(why))) {
-        VAR_SET_ERR(c, "var_convstack_fwd: %s", why);
+    if (common_error(kind, params, image, image_is_u8, image_bstride, B, workspace, workspace_bytes, flags, why, sizeof(why))) {
+        VAR_SET_ERR(c, "%s: %s", entry, why);
         return VAR_ERR_ARG;
     }
-    if (!feat) { VAR_SET_ERR(c, "var_convstack_fwd: feat is NULL (only `saved` may be)"); return VAR_ERR_ARG; }
+    if (!feat) { VAR_SET_ERR(c, "%s: feat is NULL (only `saved` may be)", entry); return VAR_ERR_ARG; }
     if (!al16(feat) || !al16(saved) || !al16(workspace)) {
-        VAR_SET_ERR(c, "var_convstack_fwd: feat, saved and the workspace must be 16-byte aligned");
+        VAR_SET_ERR(c, "%s: feat, saved and the workspace must be 16-byte aligned", entry);
         return VAR_ERR_ARG;
     }
     VAR_HIP_CHECK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const Stack& st = kStacks[kind];
     const Shapes sh = shapes_of(st);
-    const Layout lay = layout_of(st, B);
+    const bool bf = (flags & kFlagBf16) && !st.small;
+    const Layout lay = layout_of(st, B, flags & kFlagBf16);
     float* ws = (float*)workspace;
     float* acts = saved ? saved : ws + lay.acts;
     const void* x = image;
@@ -462,7 +501,10 @@ extern "C" int var_convstack_fwd(var_ctx* c, void* stream, int kind, const float
         if (st.small) {
             rc = small_fwd(c, s, small_of(d, geo_stride(L.geo), geo_pad(L.geo)), u8, x, w, b, y);
         } else {
-            CS_GEO(L.geo, u8, (rc = conv_fwd<G, true>(c, s, d, x, w, b, y)), (rc = conv_fwd<G, false>(c, s, d, x, w, b, y)))
+            int t2 = 1;                                  // 1: tier 2 has no kernel of this shape
+            if (bf && t2_candidate(st, l)) t2 = img_bf16_conv_shape(c, s, L.cin, L.cout, sh.hin[l], 0, (const float*)x, w, b, nullptr, y, B, ws + lay.tab);
+            if (t2 != 1) rc = t2;
+            else { CS_GEO(L.geo, u8, bf, (rc = conv_fwd<G, true, BF>(c, s, d, x, w, b, y)), (rc = conv_fwd<G, false, BF>(c, s, d, x, w, b, y))) }
         }
         if (rc != VAR_OK) return rc;
         x = y;
@@ -482,37 +524,39 @@ extern "C" int var_convstack_fwd(var_ctx* c, void* stream, int kind, const float
     return VAR_OK;
 }
 
-extern "C" int var_convstack_bwd(var_ctx* c, void* stream, int kind, const float* const* params, const void* image, int image_is_u8,
-                                 long image_bstride, int B, const float* saved, const float* d_feat, float* grads_flat,
-                                 void* workspace, long workspace_bytes) {
+int bwd_impl(const char* entry, var_ctx* c, void* stream, int kind, const float* const* params, const void* image, int image_is_u8,
+             long image_bstride, int B, const float* saved, const float* d_feat, float* grads_flat, void* workspace,
+             long workspace_bytes, float* d_saved, int flags) {
     if (!c) return VAR_ERR_ARG;
     char why[256];
-    if (common_error(kind, params, image, image_is_u8, image_bstride, B, workspace, workspace_bytes, why, sizeof(why))) {
-        VAR_SET_ERR(c, "var_convstack_bwd: %s", why);
+    if (common_error(kind, params, image, image_is_u8, image_bstride, B, workspace, workspace_bytes, flags, why, sizeof(why))) {
+        VAR_SET_ERR(c, "%s: %s", entry, why);
         return VAR_ERR_ARG;
     }
-    if (!saved || !d_feat || !grads_flat) { VAR_SET_ERR(c, "var_convstack_bwd: saved, d_feat or grads_flat is NULL"); return VAR_ERR_ARG; }
-    if (!al16(saved) || !al16(grads_flat) || !al16(workspace)) {
-        VAR_SET_ERR(c, "var_convstack_bwd: saved, grads_flat and the workspace must be 16-byte aligned");
+    if (!saved || !d_feat || !grads_flat) { VAR_SET_ERR(c, "%s: saved, d_feat or grads_flat is NULL", entry); return VAR_ERR_ARG; }
+    if (!al16(saved) || !al16(grads_flat) || !al16(workspace) || !al16(d_saved)) {
+        VAR_SET_ERR(c, "%s: saved, grads_flat, d_saved and the workspace must be 16-byte aligned", entry);
         return VAR_ERR_ARG;
     }
     VAR_HIP_CHECK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const Stack& st = kStacks[kind];
     const Shapes sh = shapes_of(st);
-    const Layout lay = layout_of(st, B);
+    const bool bf = (flags & kFlagBf16) && !st.small;
+    const Layout lay = layout_of(st, B, flags & kFlagBf16);
     float* ws = (float*)workspace;
-    float* G2[2] = {ws + lay.ga, ws + lay.gb};
+    // g_l, the gated gradient wrt convolution l's un-pooled map: the two ping-pong regions, or its place in the caller's d_saved
+    auto g_of = [&](int l) { return d_saved ? d_saved + saved_offset(st, B, l) : ws + ((l & 1) ? lay.gb : lay.ga); };
     float *pooled = ws + lay.pooled, *gp = ws + lay.gp, *slab = ws + lay.slab, *bpart = ws + lay.bpart;
     {   // the last layer's ReLU
         const long n = (long)B * feat_floats(st);
-        hipLaunchKernelGGL(cs_relu_gate_kernel, g1(n), dim3(256), 0, s, d_feat, saved + saved_offset(st, B, st.n - 1), G2[(st.n - 1) & 1], n);
+        hipLaunchKernelGGL(cs_relu_gate_kernel, g1(n), dim3(256), 0, s, d_feat, saved + saved_offset(st, B, st.n - 1), g_of(st.n - 1), n);
         CS_CHECK(c);
     }
     for (int l = st.n - 1; l >= 0; --l) {
         const Conv& L = st.L[l];
         const ConvDims d = dims_of(st, sh, l, B, image_bstride);
-        const float* gy = G2[l & 1];
+        const float* gy = g_of(l);
         const bool u8 = l == 0 && image_is_u8;
         // the layer's input: the image, the map below, or that map pooled again
         const void* x = image;
@@ -527,21 +571,27 @@ extern "C" int var_convstack_bwd(var_ctx* c, void* stream, int kind, const float
         }
         const int ns = wgrad_split(st, sh, l, B), MN = L.cin * 9 * L.cout;
         int rc = VAR_OK;
-        if (st.small) {
-            rc = small_wgrad(c, s, small_of(d, geo_stride(L.geo), geo_pad(L.geo)), u8, x, gy, slab, ns);
+        float* dw = grads_flat + grad_offset(st, 2 * l);
+        if (bf && t2_candidate(st, l) && img_bf16_wgrad_slab_floats(L.cin, L.cout, sh.hin[l], B) > 0) {
+            rc = img_bf16_wgrad_shape(c, s, L.cin, L.cout, sh.hin[l], (const float*)x, gy, dw, slab, B);      // (its own fold, stored)
+            if (rc != VAR_OK) return rc;
         } else {
-            CS_GEO(L.geo, u8, (rc = conv_wgrad<G, true>(c, s, d, x, gy, slab, ns)), (rc = conv_wgrad<G, false>(c, s, d, x, gy, slab, ns)))
+            if (st.small) {
+                rc = small_wgrad(c, s, small_of(d, geo_stride(L.geo), geo_pad(L.geo)), u8, x, gy, slab, ns);
+            } else {
+                CS_GEO(L.geo, u8, bf, (rc = conv_wgrad<G, true, BF>(c, s, d, x, gy, slab, ns)), (rc = conv_wgrad<G, false, BF>(c, s, d, x, gy, slab, ns)))
+            }
+            if (rc != VAR_OK) return rc;
+            rc = fold(c, s, dw, slab, MN, ns, MN);
+            if (rc != VAR_OK) return rc;
         }
-        if (rc != VAR_OK) return rc;
-        rc = fold(c, s, grads_flat + grad_offset(st, 2 * l), slab, MN, ns, MN);
-        if (rc != VAR_OK) return rc;
         const int inner = sh.hout[l] * sh.hout[l];
         hipLaunchKernelGGL(cs_chan_sum_kernel, dim3(L.cout, kChanChunks), dim3(256), 0, s, gy, bpart, B, L.cout, inner);
         CS_CHECK(c);
         rc = fold(c, s, grads_flat + grad_offset(st, 2 * l + 1), bpart, L.cout, kChanChunks, L.cout);
         if (rc != VAR_OK) return rc;
         if (!l) break;                                   // the observations carry no gradient: conv 1 has no data gradient
-        float* dx = pooled_in ? gp : G2[(l - 1) & 1];
+        float* dx = pooled_in ? gp : g_of(l - 1);
         const float* mask = pooled_in ? nullptr : below;
         const float* w = params[2 * l];
         if (st.small) {                                  // (no pool in the small stack: mask is the map below)
@@ -549,14 +599,42 @@ extern "C" int var_convstack_bwd(var_ctx* c, void* stream, int kind, const float
             hipLaunchKernelGGL(cs_small_dgrad_kernel, g1((long)B * L.cin * sh.hin[l] * sh.hin[l]), dim3(256), 0, s, sd, gy, w, mask, dx);
             CS_CHECK(c);
         } else {
-            CS_GEO(L.geo, false, (void)0, (rc = conv_dgrad<G>(c, s, d, gy, w, dx, mask)))
+            int t2 = 1;
+            if (bf && t2_candidate(st, l)) t2 = img_bf16_conv_shape(c, s, L.cin, L.cout, sh.hin[l], 1, gy, w, nullptr, mask, dx, B, ws + lay.tab);
+            if (t2 != 1) rc = t2;
+            else { CS_GEO(L.geo, false, bf, (void)0, (rc = conv_dgrad<G, BF>(c, s, d, gy, w, dx, mask))) }
         }
         if (rc != VAR_OK) return rc;
         if (pooled_in) {
             const long n = (long)B * L.cin * sh.hin[l] * sh.hin[l];
-            hipLaunchKernelGGL(cs_pool_relu_bwd_kernel, g1(n), dim3(256), 0, s, below, gp, G2[(l - 1) & 1], n, sh.hout[l - 1], sh.hin[l]);
+            hipLaunchKernelGGL(cs_pool_relu_bwd_kernel, g1(n), dim3(256), 0, s, below, gp, g_of(l - 1), n, sh.hout[l - 1], sh.hin[l]);
             CS_CHECK(c);
         }
     }
     return VAR_OK;
+}
+}  // namespace
+
+extern "C" int var_convstack_fwd_ex(var_ctx* c, void* stream, int kind, const float* const* params, const void* image, int image_is_u8,
+                                    long image_bstride, int B, float* feat, float* saved, void* workspace, long workspace_bytes,
+                                    int flags) {
+    return fwd_impl("var_convstack_fwd_ex", c, stream, kind, params, image, image_is_u8, image_bstride, B, feat, saved, workspace,
+                    workspace_bytes, flags);
+}
+extern "C" int var_convstack_fwd(var_ctx* c, void* stream, int kind, const float* const* params, const void* image, int image_is_u8,
+                                 long image_bstride, int B, float* feat, float* saved, void* workspace, long workspace_bytes) {
+    return fwd_impl("var_convstack_fwd", c, stream, kind, params, image, image_is_u8, image_bstride, B, feat, saved, workspace,
+                    workspace_bytes, 0);
+}
+extern "C" int var_convstack_bwd_ex(var_ctx* c, void* stream, int kind, const float* const* params, const void* image, int image_is_u8,
+                                    long image_bstride, int B, const float* saved, const float* d_feat, float* grads_flat,
+                                    void* workspace, long workspace_bytes, float* d_saved, int flags) {
+    return bwd_impl("var_convstack_bwd_ex", c, stream, kind, params, image, image_is_u8, image_bstride, B, saved, d_feat, grads_flat,
+                    workspace, workspace_bytes, d_saved, flags);
+}
+extern "C" int var_convstack_bwd(var_ctx* c, void* stream, int kind, const float* const* params, const void* image, int image_is_u8,
+                                 long image_bstride, int B, const float* saved, const float* d_feat, float* grads_flat,
+                                 void* workspace, long workspace_bytes) {
+    return bwd_impl("var_convstack_bwd", c, stream, kind, params, image, image_is_u8, image_bstride, B, saved, d_feat, grads_flat,
+                    workspace, workspace_bytes, nullptr, 0);
 }

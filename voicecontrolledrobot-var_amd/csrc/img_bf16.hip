@@ -376,8 +376,9 @@ __global__ void __launch_bounds__(256, 2) c3w_kernel(const float* __restrict__ x
     }
 }
 
-// dW (CO, CI, 3, 3) += the workgroups' slabs (tap, co, ci), in workgroup order: 16 slab elements x 16 slab chains per block
-__global__ void __launch_bounds__(256) c3w_fold_kernel(const float* __restrict__ slab, float* __restrict__ dw, int nslabs, int CO, int CI) {
+// dW (CO, CI, 3, 3) += (store: =) the workgroups' slabs (tap, co, ci), in workgroup order: 16 slab elements x 16 slab chains per block
+__global__ void __launch_bounds__(256) c3w_fold_kernel(const float* __restrict__ slab, float* __restrict__ dw, int nslabs, int CO, int CI,
+                                                       int store) {
     const int n = 9 * CO * CI, i = blockIdx.x * 16 + (threadIdx.x & 15), g = threadIdx.x >> 4;
     float a = 0.f;
     if (i < n)
@@ -390,12 +391,13 @@ __global__ void __launch_bounds__(256) c3w_fold_kernel(const float* __restrict__
 #pragma unroll
         for (int k = 0; k < 16; ++k) v += red[k][threadIdx.x];
         const int ci = i % CI, co = (i / CI) % CO, tap = i / (CI * CO);
-        dw[((long)co * CI + ci) * 9 + tap] += v;
+        float* q = dw + ((long)co * CI + ci) * 9 + tap;
+        *q = store ? v : *q + v;
     }
 }
 
 template <int CI, int CO, int H, int TR>
-int c3w_launch(var_ctx* c, hipStream_t s, const float* x, const float* gy, float* dw, float* slab, int B) {
+int c3w_launch(var_ctx* c, hipStream_t s, const float* x, const float* gy, float* dw, float* slab, int B, int store) {
     using G = C3W<CI, CO, H, TR>;
     static unsigned attr = 0;      // bit d: set on device d (function attributes are per device)
     if (!(attr & var_dev_bit(c))) {
@@ -405,7 +407,7 @@ int c3w_launch(var_ctx* c, hipStream_t s, const float* x, const float* gy, float
     const int ntiles = B * G::TILES, grid = ntiles < 512 ? ntiles : 512;
     hipLaunchKernelGGL((c3w_kernel<CI, CO, H, TR>), dim3(grid), dim3(256), G::LDSB, s, x, gy, slab, B);
     VAR_HIP_CHECK(c, hipGetLastError());
-    hipLaunchKernelGGL(c3w_fold_kernel, dim3((9 * CO * CI + 15) / 16), dim3(256), 0, s, slab, dw, grid, CO, CI);
+    hipLaunchKernelGGL(c3w_fold_kernel, dim3((9 * CO * CI + 15) / 16), dim3(256), 0, s, slab, dw, grid, CO, CI, store);
     VAR_HIP_CHECK(c, hipGetLastError());
     return VAR_OK;
 }
@@ -480,8 +482,8 @@ __global__ void __launch_bounds__(256, 2) c1w_kernel(const unsigned char* __rest
     }
 }
 
-// dW (32, 3, 3, 3) += the slabs (co, column), in workgroup order
-__global__ void __launch_bounds__(256) c1w_fold_kernel(const float* __restrict__ slab, float* __restrict__ dw, int nslabs) {
+// dW (32, 3, 3, 3) += (store: =) the slabs (co, column), in workgroup order
+__global__ void __launch_bounds__(256) c1w_fold_kernel(const float* __restrict__ slab, float* __restrict__ dw, int nslabs, int store) {
     const int i = blockIdx.x * 16 + (threadIdx.x & 15), g = threadIdx.x >> 4;            // i = co * 32 + column
     float a = 0.f;
     for (int s = g; s < nslabs; s += 16) a += slab[(long)s * 1024 + i];
@@ -493,7 +495,7 @@ __global__ void __launch_bounds__(256) c1w_fold_kernel(const float* __restrict__
 #pragma unroll
         for (int k = 0; k < 16; ++k) v += red[k][threadIdx.x];
         const int co = i >> 5, colm = i & 31;
-        if (colm < 27) dw[co * 27 + colm] += v;
+        if (colm < 27) dw[co * 27 + colm] = store ? v : dw[co * 27 + colm] + v;
     }
 }
 
@@ -512,29 +514,76 @@ int img_bf16_pack_all(var_ctx* c, hipStream_t s, const float* w2, const float* w
     return VAR_OK;
 }
 
-// layer = 2 | 3 of the image branch at image side 96 (48 after the first pool); dgrad: x = gy, y = dx, mask = the activation whose
-// ReLU gates dx (or null); returns 1 for shapes these kernels do not cover (the caller falls back to the gather-GEMM)
-// csum / nparts (optional): *nparts x OC partial channel sums of y -- for a data gradient, the bias gradient of the layer below
+// The dispatch, by shape: a 3 x 3 / stride 1 / padding 1 convolution of cin -> cout channels over side x side maps.  dgrad: x = gy,
+// y = dx, mask = the activation whose ReLU gates dx (or null).  tab: kTabU4 uint4 of fragment table, packed here unless prepacked.
+// Returns 1 for shapes these kernels do not cover (the caller takes the gather-GEMM).
+static int c3_by_shape(var_ctx* c, hipStream_t s, int cin, int cout, int side, int dgrad, const float* x, const float* w, const float* bias,
+                       const float* mask, float* y, float* csum, int* nparts, int B, void* tab, int prepacked) {
+#define C3_GO(IC, OC, H, TR, NI, WGS)                                                                                          \
+    if (cin == IC && cout == OC && side == H)                                                                                  \
+        return dgrad ? c3_launch<OC, IC, H, TR, NI, 1, WGS>(c, s, x, w, bias, mask, y, csum, nparts, B, tab, prepacked)         \
+                     : c3_launch<IC, OC, H, TR, NI, 0, WGS>(c, s, x, w, bias, mask, y, csum, nparts, B, tab, prepacked)
+    C3_GO(32, 32, 96, 8, 1, 2);
+    C3_GO(32, 64, 48, 8, 1, 2);
+    C3_GO(64, 64, 24, 24, 1, 1);
+    C3_GO(64, 128, 12, 12, 2, 1);
+    // armNet_VAR.imgCNN's maps (convstack.hip, kind 0); half-image tiles at 24 x 24: 3 pixel blocks x 4 channel blocks per wave.
+    // The data gradient keeps its mask values and channel sums beside the accumulators: a smaller tile where TR of the forward spills
+#define C3_GO2(IC, OC, H, TRF, WGSF, TRD, WGSD)                                                                                \
+    if (cin == IC && cout == OC && side == H)                                                                                  \
+        return dgrad ? c3_launch<OC, IC, H, TRD, 1, 1, WGSD>(c, s, x, w, bias, mask, y, csum, nparts, B, tab, prepacked)        \
+                     : c3_launch<IC, OC, H, TRF, 1, 0, WGSF>(c, s, x, w, bias, mask, y, csum, nparts, B, tab, prepacked)
+    C3_GO2(64, 64, 48, 8, 2, 4, 2);
+    C3_GO(64, 128, 24, 12, 1, 1);
+    C3_GO2(128, 128, 24, 12, 1, 8, 1);
+#undef C3_GO2
+#undef C3_GO
+    return 1;
+}
+// the weight gradient of the same convolutions, dw (+)= ; slab: img_bf16_wgrad_slab_floats
+static int c3w_by_shape(var_ctx* c, hipStream_t s, int cin, int cout, int side, const float* x, const float* gy, float* dw, float* slab,
+                        int B, int store) {
+    if (cin == 32 && cout == 32 && side == 96) return c3w_launch<32, 32, 96, 4>(c, s, x, gy, dw, slab, B, store);
+    if (cin == 32 && cout == 64 && side == 48) return c3w_launch<32, 64, 48, 4>(c, s, x, gy, dw, slab, B, store);
+    if (cin == 64 && cout == 64 && side == 48) return c3w_launch<64, 64, 48, 4>(c, s, x, gy, dw, slab, B, store);
+    return 1;
+}
+
+// layer = 2..5 of the iTHOR pretext model's image branch at image side 96 (`side` is the layer's own map side); table
+// 2 (layer - 2) + dgrad of ws; csum / nparts (optional): *nparts x OC partial channel sums of y -- for a data gradient, the bias
+// gradient of the layer below
 int img_bf16_conv(var_ctx* c, hipStream_t s, int layer, int side, int dgrad, const float* x, const float* w, const float* bias,
                   const float* mask, float* y, float* csum, int* nparts, int B, void* ws, int prepacked) {
-    void* tab = (uint4*)ws + (2 * (layer - 2) + (dgrad ? 1 : 0)) * kTabU4;      // (layer 2..5 checked below)
-#define C3_GO(IC, OC, H, TR, NI, WGS)                                                                                          \
-    return dgrad ? c3_launch<OC, IC, H, TR, NI, 1, WGS>(c, s, x, w, bias, mask, y, csum, nparts, B, tab, prepacked)             \
-                 : c3_launch<IC, OC, H, TR, NI, 0, WGS>(c, s, x, w, bias, mask, y, csum, nparts, B, tab, prepacked)
-    if (layer == 2 && side == 96) { C3_GO(32, 32, 96, 8, 1, 2); }
-    if (layer == 3 && side == 48) { C3_GO(32, 64, 48, 8, 1, 2); }
-    if (layer == 4 && side == 24) { C3_GO(64, 64, 24, 24, 1, 1); }
-    if (layer == 5 && side == 12) { C3_GO(64, 128, 12, 12, 2, 1); }
-#undef C3_GO
-    return 1;                                                   // not covered
+    constexpr int IC[4] = {32, 32, 64, 64}, OC[4] = {32, 64, 64, 128}, HS[4] = {96, 48, 24, 12};
+    if (layer < 2 || layer > 5 || side != HS[layer - 2]) return 1;
+    void* tab = (uint4*)ws + (2 * (layer - 2) + (dgrad ? 1 : 0)) * kTabU4;
+    return c3_by_shape(c, s, IC[layer - 2], OC[layer - 2], side, dgrad, x, w, bias, mask, y, csum, nparts, B, tab, prepacked);
 }
 
 // dw (COUT, CIN, 3, 3) += the weight gradient of layer 2 | 3 from its input x and the gradient gy wrt its output (fp32 NCHW);
 // slab: 512 x 9*COUT*CIN floats; returns 1 for shapes not covered
 int img_bf16_wgrad(var_ctx* c, hipStream_t s, int layer, int side, const float* x, const float* gy, float* dw, float* slab, int B) {
-    if (layer == 2 && side == 96) return c3w_launch<32, 32, 96, 4>(c, s, x, gy, dw, slab, B);
-    if (layer == 3 && side == 48) return c3w_launch<32, 64, 48, 4>(c, s, x, gy, dw, slab, B);
+    if (layer == 2 && side == 96) return c3w_by_shape(c, s, 32, 32, 96, x, gy, dw, slab, B, 0);
+    if (layer == 3 && side == 48) return c3w_by_shape(c, s, 32, 64, 48, x, gy, dw, slab, B, 0);
     return 1;
+}
+
+// The same kernels for a caller that names the shape (convstack.hip): the fragment table is packed inside the call into `tab`
+// (img_bf16_table_bytes of the caller's workspace: nothing packed outlives the call), the weight gradient is STORED.
+long img_bf16_table_bytes() { return kTabU4 * 16L; }
+int img_bf16_conv_shape(var_ctx* c, hipStream_t s, int cin, int cout, int side, int dgrad, const float* x, const float* w,
+                        const float* bias, const float* mask, float* y, int B, void* tab) {
+    return c3_by_shape(c, s, cin, cout, side, dgrad, x, w, bias, mask, y, nullptr, nullptr, B, tab, 0);
+}
+// floats of slab the stored weight gradient needs at batch B (a function of the shape alone), 0 where the shape is not covered
+long img_bf16_wgrad_slab_floats(int cin, int cout, int side, int B) {
+    const bool covered = (cin == 32 && cout == 32 && side == 96) || (cin == 32 && cout == 64 && side == 48) || (cin == 64 && cout == 64 && side == 48);
+    if (!covered) return 0;
+    const long ntiles = (long)B * (side / 4);
+    return (ntiles < 512 ? ntiles : 512) * 9L * cout * cin;
+}
+int img_bf16_wgrad_shape(var_ctx* c, hipStream_t s, int cin, int cout, int side, const float* x, const float* gy, float* dw, float* slab, int B) {
+    return c3w_by_shape(c, s, cin, cout, side, x, gy, dw, slab, B, 1);
 }
 
 // layer 1's weight gradient from the u8 image batch (bstride bytes between images, 3 planes of side x side first) and the
@@ -544,7 +593,7 @@ int img_bf16_wgrad1(var_ctx* c, hipStream_t s, int side, const void* image, long
     const int ntiles = B * (96 / 8), grid = ntiles < 512 ? ntiles : 512;
     hipLaunchKernelGGL((c1w_kernel<96, 8>), dim3(grid), dim3(256), 0, s, (const unsigned char*)image, bstride, gy, slab, B);
     VAR_HIP_CHECK(c, hipGetLastError());
-    hipLaunchKernelGGL(c1w_fold_kernel, dim3(1024 / 16), dim3(256), 0, s, slab, dw, grid);
+    hipLaunchKernelGGL(c1w_fold_kernel, dim3(1024 / 16), dim3(256), 0, s, slab, dw, grid, 0);
     VAR_HIP_CHECK(c, hipGetLastError());
     return VAR_OK;
 }

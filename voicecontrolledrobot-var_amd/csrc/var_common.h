@@ -458,3 +458,10 @@ int img_bf16_conv(var_ctx* c, hipStream_t s, int layer, int side, int dgrad, con
 int img_bf16_pack_all(var_ctx* c, hipStream_t s, const float* w2, const float* w3, const float* w4, const float* w5, void* ws);
 int img_bf16_wgrad(var_ctx* c, hipStream_t s, int layer, int side, const float* x, const float* gy, float* dw, float* slab, int B);
 int img_bf16_wgrad1(var_ctx* c, hipStream_t s, int side, const void* image, long bstride, const float* gy, float* dw, float* slab, int B);
+// the same kernels by shape (cin -> cout channels over side x side maps), for convstack.hip: the fragment table is packed inside the
+// call into `tab` (img_bf16_table_bytes), the weight gradient is stored, not accumulated; 1 where the shape is not covered
+long img_bf16_table_bytes();
+int img_bf16_conv_shape(var_ctx* c, hipStream_t s, int cin, int cout, int side, int dgrad, const float* x, const float* w,
+                        const float* bias, const float* mask, float* y, int B, void* tab);
+long img_bf16_wgrad_slab_floats(int cin, int cout, int side, int B);
+int img_bf16_wgrad_shape(var_ctx* c, hipStream_t s, int cin, int cout, int side, const float* x, const float* gy, float* dw, float* slab, int B);
