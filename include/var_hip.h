@@ -406,6 +406,35 @@ int var_ithor_policy_forward(var_ctx* ctx, void* stream, const float* params, in
 int var_ithor_policy_status(var_ctx* ctx, unsigned* word);
 int var_ithor_policy_clear_status(var_ctx* ctx);
 
+/* The acting forwards with bf16 operands ---------------------------------------------------------------------------------
+ * var_armnet_forward_ex / var_ithor_policy_forward_ex take the argument lists above plus `flags`; the entries above are
+ * _ex(..., 0) and keep their bits.
+ *   flags bit 0   bf16 operands in every convolution of imgCNN (conv 1-8 of armNet_VAR, conv 1-6 of ai2thorNet_VAR), with the
+ *       rounding points of var_convstack_fwd_ex's flags bit 0 (below), so that the rollout's old log-probabilities and the PPO
+ *       update's evaluation come from one function: layer l computes relu(conv(bf16(x_l), bf16(w_l)) + b_l); x_1 is the float
+ *       image exactly as the fp32 path forms it from bytes ((float)u8 / 255.f, or the float input), x_l the stored fp32 map
+ *       below, pooled where a pool follows; rounding is to nearest even; products accumulate in fp32; bias and ReLU act in
+ *       fp32; pools act on fp32 values; everything stored stays fp32, in the layouts and var_debug_buffer names of the fp32
+ *       forward.  The iTHOR occupancy convolutions, the MLP chain and the per-layer MLP, the GRU step, the head and
+ *       var_policy_dist stay fp32.  Kernels, up to 64 images: the 3x3 / stride 1 / pad 1 band layers behind conv 1 (conv 2-6 of
+ *       armNet_VAR, conv 2-5 of ai2thorNet_VAR) run on csrc/c3f_bf16.h's band kernel -- the band rounded as it is written to LDS
+ *       into a channel-innermost bf16 image, the filters packed as bf16 A fragments inside conv 1's launch,
+ *       v_mfma_f32_16x16x32_bf16, the fp32 kernel's epilogue and fused pool; conv 1 and the small last layers (conv 7 / 8, iTHOR's
+ *       conv 6) keep csrc/c3f.h's fp32 kernels and round both operands where they stage them -- a product of two bf16 values is
+ *       exact in fp32, so that IS the definition above, summed in the fp32 forward's order.  Beyond 64 images every layer takes
+ *       the gather-GEMM with its operands rounded on the way into v_mfma_f32_32x32x16_bf16.
+ *   A plan (var_armnet_plan / var_ithor_policy_plan) serves both precisions; the filter tables are re-packed inside the first
+ *   launch of every call in the call's precision.  Any other flag bit is refused: VAR_ERR_ARG, the entry's name first in the
+ *   message, nothing launched or written. */
+int var_armnet_forward_ex(var_ctx* ctx, void* stream, const float* params, const void* image, int image_is_u8,
+                          long image_bstride, const float* image_feat, const float* robot_pose,
+                          const float* goal_sound_feat, const float* rnn_hxs, const float* masks, int B,
+                          float* value, float* actor_features, float* action_mean, float* rnn_hxs_out, int flags);
+int var_ithor_policy_forward_ex(var_ctx* ctx, void* stream, const float* params, int n_actions, const void* image,
+                                int image_is_u8, long image_bstride, const void* occupancy, int occupancy_is_u8,
+                                const float* image_feat, const float* goal_sound_feat, const float* rnn_hxs, const float* masks,
+                                int B, float* value, float* actor_features, float* logits, float* rnn_hxs_out, int flags);
+
 /* The distribution tail of Policy.act -------------------------------------------------------------------------------
  * What follows the forward in models/ppo/model.py:59-69: the action (dist.sample() or dist.mode()) and dist.log_probs(action)
  * of DiagGaussian / Categorical (models/ppo/distributions.py:7-33, 60-84), ONE launch instead of about a dozen on (B,n)

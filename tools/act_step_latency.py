@@ -10,8 +10,13 @@
       with the inputs already in step.obs / step.masks -- the figure to hold against (b) and (c)
 Each figure is the median of --iters calls (host clock around call + synchronise), repeated --repeats times with the legs
 alternating; the JSON carries the median of the repeats and their spread (max - min).
-    python3 tools/act_step_latency.py [--envs 8] [--iters 200] [--repeats 3] [--out profiles/act_step_latency.json]
-    rocprofv3 --kernel-trace --stats -d DIR -o act -f csv -- python3 tools/act_step_latency.py --replay-only"""
+--bf16 adds the legs of the acting forwards' bf16 mode (policy.set_acting_precision("bf16") / capture(precision="bf16"):
+b_forward_replay_bf16, d_act_step_bf16, d_act_step_inputs_in_place_bf16), alternated with the fp32 legs in the same process under
+the same protocol -- the fp32 legs are the yardstick --, and per policy the speed-up of the replayed step and whether the bf16 step
+is no slower than the fp32 one by more than the two legs' spread.  Writes profiles/act_step_bf16_latency.json.
+    python3 tools/act_step_latency.py [--envs 8] [--iters 200] [--repeats 3] [--bf16] [--out profiles/act_step_latency.json]
+    rocprofv3 --kernel-trace --stats -d DIR -o act -f csv -- python3 tools/act_step_latency.py --replay-only [--bf16]
+(--replay-only --bf16 replays the steps of both precisions: c3f_kernel / c3b_kernel per layer in one kernel trace)"""
 import argparse
 import json
 import os
@@ -85,18 +90,33 @@ def capture(body):
     return graph
 
 
-def legs(which, B, replay_only):
+def legs(which, B, replay_only, bf16=False):
     import torch
     m, obs, hxs, masks = build(which, B)
-    step = m.capture(B, seed=0)
-    for k, v in obs.items():
-        step.obs[k].copy_(v)
-    step.masks.copy_(masks)
-    out = {"d_act_step": lambda: step(obs, masks), "d_act_step_inputs_in_place": lambda: step(step.obs, step.masks)}
+    out = {}
+
+    def step_legs(precision, tag):
+        step = m.capture(B, seed=0, precision=precision)
+        for k, v in obs.items():
+            step.obs[k].copy_(v)
+        step.masks.copy_(masks)
+        out["d_act_step" + tag] = lambda: step(obs, masks)
+        out["d_act_step_inputs_in_place" + tag] = lambda: step(step.obs, step.masks)
+
+    def forward_leg(precision, tag):
+        m.set_acting_precision(precision)                        # (read when the call is captured, not at replay)
+        out["b_forward_replay" + tag] = capture(lambda: m._base_forward(obs, hxs, masks)).replay
+        m.set_acting_precision("fp32")
+
+    step_legs("fp32", "")
+    if bf16:
+        step_legs("bf16", "_bf16")
     if replay_only:
         return out
     out["a_eager_act"] = lambda: m.act(obs, hxs, masks)
-    out["b_forward_replay"] = capture(lambda: m._base_forward(obs, hxs, masks)).replay
+    forward_leg("fp32", "")
+    if bf16:
+        forward_leg("bf16", "_bf16")
 
     def act_body():                                              # act() as it stands + the state fed back
         hxs.copy_(m.act(obs, hxs, masks)[3])
@@ -115,12 +135,15 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--replay-only", action="store_true", help="only the new step's replays (for a kernel trace)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "act_step_latency.json"))
+    ap.add_argument("--bf16", action="store_true", help="add the bf16 legs beside the fp32 ones")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "act_step_bf16_latency.json" if a.bf16 else "act_step_latency.json")
     import torch
     result = {"envs": a.envs, "iters": a.iters, "repeats": a.repeats, "device": torch.cuda.get_device_name(0), "unit": "us"}
     for which in ("arm", "ithor"):
-        fns = legs(which, a.envs, a.replay_only)
+        fns = legs(which, a.envs, a.replay_only, a.bf16)
         runs = {k: [] for k in fns}
         for _ in range(a.repeats):
             for k in sorted(fns):
@@ -135,6 +158,12 @@ def main():
             r["d_minus_b"] = round(med("d_act_step_inputs_in_place") - med("b_forward_replay"), 1)
         if med("c_user_graph_of_act") is not None:
             r["c_minus_d"] = round(med("c_user_graph_of_act") - med("d_act_step_inputs_in_place"), 1)
+        if a.bf16:
+            for k in ("d_act_step_inputs_in_place", "d_act_step", "b_forward_replay"):
+                if med(k) is not None and med(k + "_bf16") is not None:
+                    slack = max(r[k]["spread"], r[k + "_bf16"]["spread"])
+                    r[k + "_fp32_over_bf16"] = round(med(k) / med(k + "_bf16"), 3)
+                    r[k + "_bf16_no_slower_within_spread"] = bool(med(k + "_bf16") <= med(k) + slack)
         result[which] = r
     print(json.dumps(result))
     if not a.replay_only:

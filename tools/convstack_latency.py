@@ -11,7 +11,10 @@ work that ends in a device synchronise.  Writes profiles/convstack_latency.json.
 them in the same process (the yardstick is the fp32 conv_stack_eval leg), and then records the mode's effect on PPO at (T, N) =
 (100, 4) for both policies with tests/convstack_cpu.policy_params weights: |ratio - 1| of the importance ratio when the old
 log-probabilities come from the fp32 evaluation (which stands for the fp32 acting forward) and the new ones from the bf16
-evaluation, and each gradient array's distance from the fp32 leg's.  Writes profiles/convstack_bf16_latency.json.
+evaluation, and each gradient array's distance from the fp32 leg's; next to that fp32 stand-in row, two pairings with REAL acting
+output on the same observations: the log-probabilities policy.act leaves at acting precision "fp32" and at "bf16"
+(policy.set_acting_precision; rows of N observations through the acting forward, the rollout's hidden states) against the bf16
+evaluation of the same actions.  Writes profiles/convstack_bf16_latency.json.
 
 usage: python tools/convstack_latency.py [--runs 30] [--repeats 3] [--out profiles/convstack_latency.json] [--only-hip]
            [--configs 0:400,...] [--bf16]
@@ -122,6 +125,7 @@ def ppo_effect(kind, seed=9):
                     actions = mean + logstd.exp() * rn(M, n_act)
                 logp[prec] = (-0.5 * ((actions - mean) / logstd.exp()) ** 2 - logstd - 0.9189385332046727).sum(-1, keepdim=True)
     ratio = torch.exp(logp["bf16"] - logp["fp32"])
+    acting = acting_pairings(kind, pol, obs, hxs, masks, actions, logp["bf16"], n_act)
     sample = (obs, hxs, actions, rn(M, 1), rn(M, 1), masks.view(M, 1), logp["fp32"], rn(M, 1))
     agent = var_amd.PPO(pol, 0.2, 1, 1, 0.5, 0.01, lr=1e-4, eps=1e-5, max_grad_norm=0.5)
     grads = {}
@@ -133,7 +137,32 @@ def ppo_effect(kind, seed=9):
     dist_g = {n: float((grads["bf16"][n] - v).abs().max() / v.abs().max()) for n, v in grads["fp32"].items()}
     return {"what": "effect of bf16 evaluation on the first PPO minibatch after a rollout", "kind": kind, "T": T, "N": N,
             "max_abs_ratio_minus_1": float((ratio - 1).abs().max()), "mean_abs_ratio_minus_1": float((ratio - 1).abs().mean()),
+            "acting_log_probabilities_against_bf16_evaluation": acting,
             "gradient_distance_from_fp32": dist_g, "largest_gradient_distance": max(dist_g.values())}
+
+
+def acting_pairings(kind, pol, obs, hxs, masks, actions, logp_eval, n_act):
+    """|ratio - 1| of the first minibatch when the old log-probabilities are what the ACTING forward computes (the real entry, N
+    rows per call, hidden state carried and masked as in the rollout) at acting precision fp32 (the pairing before the acting
+    forwards had a bf16 mode) and bf16 (set_acting_precision("bf16")), the new ones from the bf16 evaluation."""
+    out = {}
+    with torch.no_grad():
+        for prec in ("fp32", "bf16"):
+            pol.set_acting_precision(prec)
+            h, logps = hxs, []
+            for t in range(T):
+                rows = slice(t * N, (t + 1) * N)
+                _value, _feats, head, h = pol._base_forward({k: v[rows] for k, v in obs.items()}, h, masks[t].view(N, 1))
+                a = actions[rows]
+                if kind:
+                    logps.append(torch.log_softmax(head, dim=-1).gather(1, a))
+                else:
+                    logstd = pol.dist.logstd._bias.view(1, -1)
+                    logps.append((-0.5 * ((a - head) / logstd.exp()) ** 2 - logstd - 0.9189385332046727).sum(-1, keepdim=True))
+            r = torch.exp(logp_eval - torch.cat(logps))
+            out[prec + "_acting"] = {"max_abs_ratio_minus_1": float((r - 1).abs().max()), "mean_abs_ratio_minus_1": float((r - 1).abs().mean())}
+        pol.set_acting_precision("fp32")
+    return out
 
 
 def main():

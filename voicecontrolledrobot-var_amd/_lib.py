@@ -79,6 +79,7 @@ _SIGNATURES = {
     "var_armnet_param_count": (_i, []),
     "var_armnet_plan": (_i, [_vp, _i]),
     "var_armnet_forward": (_i, [_vp, _vp, _vp, _vp, _i, _l, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "var_armnet_forward_ex": (_i, [_vp, _vp, _vp, _vp, _i, _l, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i]),
     "var_armnet_status": (_i, [_vp, _vp]),
     "var_join_status": (_i, [_vp, _vp]),
     "var_set_reward_dot": (_i, [_vp, _vp, _vp]),
@@ -87,6 +88,7 @@ _SIGNATURES = {
     "var_ithor_policy_param_count": (_i, [_i]),
     "var_ithor_policy_plan": (_i, [_vp, _i]),
     "var_ithor_policy_forward": (_i, [_vp, _vp, _vp, _i, _vp, _i, _l, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "var_ithor_policy_forward_ex": (_i, [_vp, _vp, _vp, _i, _vp, _i, _l, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i]),
     "var_ithor_policy_status": (_i, [_vp, _vp]),
     "var_ithor_policy_clear_status": (_i, [_vp]),
     "var_policy_dist": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),

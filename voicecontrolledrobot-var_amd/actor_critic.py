@@ -14,12 +14,25 @@ bind_trunk gives .base a differentiable forward (imgCNN in PyTorch, everything b
 IthorNetPolicy is the same for base 'ai2thor_VAR' (models/RL/ai2thor_RL_model.py:ai2thorNet_VAR, iTHOR configuration,
 Discrete actions: 64 tensors, var_ithor_policy_forward in csrc/ithor_policy.hip, sampling through
 torch.distributions.Categorical as the reference's FixedCategorical).  Policy() dispatches on `base` as the reference's
-Policy does."""
+Policy does.
+set_acting_precision("bf16") (attribute acting_precision, default "fp32"; capture(..., precision=...) for one step) makes act,
+get_value and capture round the operands of every imgCNN convolution to bf16 where bind_convs(policy, precision="bf16") rounds them
+in the PPO update's evaluation (var_*_forward_ex flags bit 0): acting and evaluation then compute one function."""
 import numpy as np
 import torch
 import torch.nn as nn
 
 from ._lib import Context, VarHipError, current_stream_handle, ptr
+
+# the acting forwards' precisions -> flags of var_*_forward_ex (bit 0: bf16 operands in every imgCNN convolution, the rounding
+# points of conv_stack_eval's / bind_convs' precision="bf16")
+PRECISIONS = {"fp32": 0, "bf16": 1}
+
+
+def _flags(precision, who):
+    if precision not in PRECISIONS:
+        raise VarHipError(f"{who}: precision {precision!r} is neither 'fp32' nor 'bf16'")
+    return PRECISIONS[precision]
 
 
 def _ortho(m, gain):
@@ -125,9 +138,19 @@ class _ArenaPolicy(nn.Module):
     # _n_head, the width of the distribution's Linear layer.
     def _finish_init(self, count_args, n_head):
         self._count_args, self._n_head = count_args, n_head
+        self.acting_precision = "fp32"
         self._flat = None
         self._plan = 0
         self._flatten_params()
+
+    def set_acting_precision(self, precision):
+        """"fp32" (the default) or "bf16": what act, get_value and capture compute imgCNN with.  "bf16" rounds the operands of
+        every imgCNN convolution where bind_convs(policy, precision="bf16") rounds them in the PPO update's evaluation
+        (include/var_hip.h, var_*_forward_ex flags bit 0), so the rollout's log-probabilities and the update's first evaluation
+        come from one function; everything behind the convolutions stays fp32.  Returns the policy."""
+        _flags(precision, "set_acting_precision")
+        self.acting_precision = precision
+        return self
 
     def _call(self, c, name, *args):
         fn = f"{self._C}_{name}"
@@ -169,14 +192,15 @@ class _ArenaPolicy(nn.Module):
         self._ensure_plan(c, B)
         out = lambda n: torch.empty((B, n), dtype=torch.float32, device=flat.device)   # noqa: E731
         value, feats, head_out, hout = out(1), out(128), out(self._n_head) if head else None, out(H)
-        self._launch_forward(c, obs, hxs, m, value, feats, head_out, hout)
+        self._launch_forward(c, obs, hxs, m, value, feats, head_out, hout, _flags(self.acting_precision, "acting_precision"))
         return value, feats, head_out, hout
 
-    def capture(self, batch, deterministic=False, seed=0, image_dtype=torch.uint8):
+    def capture(self, batch, deterministic=False, seed=0, image_dtype=torch.uint8, precision=None):
         """act() for a fixed number of envs as one replayed HIP graph with on-device sampling: see ActStep.  image_dtype:
         what the image inputs ('image', iTHOR's 'occupancy') will be fed as (uint8, or float32 already divided by 255).
-        'image_feat' and 'goal_sound_feat' may be the device tensors IntrinsicReward.step returned: no host round trip."""
-        return ActStep(self, batch, deterministic, seed, image_dtype)
+        'image_feat' and 'goal_sound_feat' may be the device tensors IntrinsicReward.step returned: no host round trip.
+        precision: "fp32" / "bf16" for this step, default the policy's acting_precision (set_acting_precision)."""
+        return ActStep(self, batch, deterministic, seed, image_dtype, self.acting_precision if precision is None else precision)
 
     def chain_status(self):
         """Status of the small-batch (B <= 8) MLP chain launch, a persistent kernel that needs its 128 workgroups resident at
@@ -216,13 +240,16 @@ class ActStep:
     the stream of numbers is not torch's, the distributions are the same.
     obs, masks: the static input buffers; a tensor passed to step() that IS its buffer (the caller filled step.obs[...] in
     place) is not copied.  head: the action mean (B,n) / the logits (B,n) of the last step; noise: the z (B,n) / u (B,) it
-    used; rng_step: the generator step it drew from (-1 before the first sampling step; reads the device, blocking).
+    used; rng_step: the generator step it drew from (-1 before the first sampling step; reads the device, blocking);
+    precision: "fp32" / "bf16", what the captured forward computes imgCNN with (set_acting_precision; fixed at capture).
 
     Weights: the forwards re-pack their filters inside every call, so parameters updated IN PLACE (the PPO optimiser's
     step, load_state_dict) are what the next replay computes with.  The graph holds the arena's address: after .to() /
     .cuda() / anything else that moves the parameters, step() raises VarHipError -- call capture() again."""
 
-    def __init__(self, policy, batch, deterministic, seed, image_dtype):
+    def __init__(self, policy, batch, deterministic, seed, image_dtype, precision="fp32"):
+        flags = _flags(precision, "capture")
+        self.precision = precision
         if not policy._arena_intact():
             policy._flatten_params()
         flat = policy._flat
@@ -250,7 +277,7 @@ class ActStep:
         self._rng0 = torch.from_numpy(np.array([seed & 0xffffffff, seed >> 32, 0, 0], dtype=np.uint32).view(np.int32)).to(dev)
 
         def body():
-            policy._launch_forward(c, self.obs, self._hxs, self.masks, self.value, self.actor_features, self.head, self._hout)
+            policy._launch_forward(c, self.obs, self._hxs, self.masks, self.value, self.actor_features, self.head, self._hout, flags)
             c.check(c.lib.var_policy_dist(c.handle, current_stream_handle(), kind, ptr(self.head), ptr(logstd), n, B,
                                           int(self.deterministic), None, ptr(self._rng), ptr(self.noise), ptr(self.action),
                                           ptr(self.action_log_probs), ptr(self._hout), ptr(self._hxs), hidden),
@@ -340,14 +367,14 @@ class ArmNetPolicy(_ArenaPolicy):
     def recurrent_hidden_state_size(self):
         return 512
 
-    def _launch_forward(self, c, obs, hxs, masks, value, feats, mean, hout):
-        """The C call on prepared tensors (contiguous, on the arena's device)."""
+    def _launch_forward(self, c, obs, hxs, masks, value, feats, mean, hout, flags=0):
+        """The C call on prepared tensors (contiguous, on the arena's device); flags: var_armnet_forward_ex's."""
         image, B = obs['image'], obs['image'].shape[0]
-        c.check(c.lib.var_armnet_forward(c.handle, current_stream_handle(), ptr(self._flat), ptr(image),
-                                         int(image.dtype == torch.uint8), image.stride(0), ptr(obs['image_feat']),
-                                         ptr(obs['robot_pose']), ptr(obs['goal_sound_feat']), ptr(hxs), ptr(masks), B,
-                                         ptr(value), ptr(feats), ptr(mean), ptr(hout)),
-                "var_armnet_forward")
+        c.check(c.lib.var_armnet_forward_ex(c.handle, current_stream_handle(), ptr(self._flat), ptr(image),
+                                            int(image.dtype == torch.uint8), image.stride(0), ptr(obs['image_feat']),
+                                            ptr(obs['robot_pose']), ptr(obs['goal_sound_feat']), ptr(hxs), ptr(masks), B,
+                                            ptr(value), ptr(feats), ptr(mean), ptr(hout), int(flags)),
+                "var_armnet_forward_ex")
 
     def _step_spec(self, B, image_dtype):
         f = torch.float32
@@ -426,15 +453,15 @@ class IthorNetPolicy(_ArenaPolicy):
     def recurrent_hidden_state_size(self):
         return 1024
 
-    def _launch_forward(self, c, obs, hxs, masks, value, feats, logits, hout):
-        """The C call on prepared tensors (contiguous, on the arena's device)."""
+    def _launch_forward(self, c, obs, hxs, masks, value, feats, logits, hout, flags=0):
+        """The C call on prepared tensors (contiguous, on the arena's device); flags: var_ithor_policy_forward_ex's."""
         image, occ, B = obs['image'], obs['occupancy'], obs['image'].shape[0]
-        c.check(c.lib.var_ithor_policy_forward(c.handle, current_stream_handle(), ptr(self._flat), self.n_actions, ptr(image),
-                                               int(image.dtype == torch.uint8), image.stride(0), ptr(occ),
-                                               int(occ.dtype == torch.uint8), ptr(obs['image_feat']),
-                                               ptr(obs['goal_sound_feat']), ptr(hxs), ptr(masks), B,
-                                               ptr(value), ptr(feats), ptr(logits), ptr(hout)),
-                "var_ithor_policy_forward")
+        c.check(c.lib.var_ithor_policy_forward_ex(c.handle, current_stream_handle(), ptr(self._flat), self.n_actions, ptr(image),
+                                                  int(image.dtype == torch.uint8), image.stride(0), ptr(occ),
+                                                  int(occ.dtype == torch.uint8), ptr(obs['image_feat']),
+                                                  ptr(obs['goal_sound_feat']), ptr(hxs), ptr(masks), B,
+                                                  ptr(value), ptr(feats), ptr(logits), ptr(hout), int(flags)),
+                "var_ithor_policy_forward_ex")
 
     def _step_spec(self, B, image_dtype):
         f = torch.float32

@@ -267,7 +267,8 @@ def bind_convs(policy, precision="fp32"):
     actor_features, rnn_hxs, {}) that runs imgCNN (and, for ai2thor_VAR, occupancyCNNMLP's two convolutions) through
     conv_stack_eval and everything behind them through trunk_eval; returns the policy, so that PPO(bind_convs(policy), ...) reads
     like bind_trunk.  precision: conv_stack_eval's, for the stacks alone -- the trunk, the head, the parameters, their gradients and
-    the acting forwards stay fp32, so with "bf16" the importance ratio of the first minibatch after a rollout is close to 1, not 1."""
+    the acting forwards stay fp32, so with "bf16" the importance ratio of the first minibatch after a rollout is close to 1, not 1.
+    The matching acting setting is policy.set_acting_precision("bf16"): the acting forwards then round where this evaluation does."""
     _flags(precision, "bind_convs")
     base = getattr(policy, "base", None)
     if base is None:

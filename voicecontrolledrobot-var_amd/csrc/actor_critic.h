@@ -64,15 +64,15 @@ struct Lin { int w, b, in, out; };
 inline dim3 g1(long n) { return dim3((unsigned)((n + 255) / 256)); }
 constexpr long kSlab = 8L << 20;   // floats of split-K scratch
 
-// ---- the gather-GEMM path (gg.h), layer by layer; slab: kSlab floats of split-K scratch
-template <class G, bool U8>
+// ---- the gather-GEMM path (gg.h), layer by layer; slab: kSlab floats of split-K scratch; BF: gg.h's bf16 operand rounding
+template <class G, bool U8, bool BF = false>
 int conv(var_ctx* c, hipStream_t s, float* slab, const ConvDims& d, const void* x, const float* w, const float* bias, float* y) {
     ConvFwdP<G, U8, false> p{};
     p.M = d.B * d.HO * d.WO; p.N = d.COUT; p.K = d.CIN * G::KHW;
     const long out = (long)p.M * p.N;
     p.nsplit = gg_small_split(((p.M + GG_MT - 1) / GG_MT) * ((p.N + 63) / 64), p.K, out, kSlab);
     p.d = d; p.x = x; p.w = w; p.bias = bias; p.y = y; p.slab = slab; p.sstride = out;
-    RUN(gg_launch(c, s, p));
+    RUN((gg_launch<ConvFwdP<G, U8, false>, GG_KC, BF>(c, s, p)));
     if (p.nsplit > 1) {
         hipLaunchKernelGGL(gg_finish_kernel, g1(out), dim3(256), 0, s, y, slab, out, p.nsplit, out, bias, d.COUT, d.HO * d.WO, 1);
         AC_CHECK(c);

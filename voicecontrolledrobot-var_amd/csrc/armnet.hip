@@ -5,9 +5,13 @@
 // everything of Policy.act up to the sampling.  Inference only (the PPO update stays in PyTorch).  Up to 64 images the
 // convolutions run on the LDS-band kernels of c3f.h (filters re-packed per call inside conv 1's launch) and, up to 8 rows, the
 // 22 Linear layers + GRU step on the one-launch chain below; larger batches take the gather-GEMM of gg.h layer by layer with
-// the parameters in place in their state_dict() layouts.  What this forward shares with ithor_policy.hip -- the elementwise
+// the parameters in place in their state_dict() layouts.  var_armnet_forward_ex's flags bit 0 runs every convolution on operands
+// rounded to bf16 (conv 2..6 on c3f_bf16.h's band kernel, conv 1 / 7 / 8 rounding where they stage, the gather-GEMM with BF = true);
+// everything behind the convolutions is the same code in both precisions.  What this forward shares with ithor_policy.hip -- the elementwise
 // kernels, the launch helpers, the workspace, the per-layer path from the GRU step on -- lives in actor_critic.h.
 #include <string.h>
+
+#include <type_traits>
 
 #include "gg.h"
 
@@ -71,6 +75,13 @@ using ArmC3 = c3f::Cfg<32, 64, 48, 6, 1, 1, false>;
 using ArmC4 = c3f::Cfg<64, 64, 48, 6, 1, 1, true>;
 using ArmC5 = c3f::Cfg<64, 128, 24, 8, 1, 1, false>;
 using ArmC6 = c3f::Cfg<128, 128, 24, 4, 2, 2, true>;
+// the same bands on c3f_bf16.h's kernel (flags bit 0); kArmBands: the band layers among the pack's layers (bit i = conv i + 2)
+using ArmB2 = c3f::CfgB<32, 32, 96, 4, 2, 1, true>;
+using ArmB3 = c3f::CfgB<32, 64, 48, 6, 1, 1, false>;
+using ArmB4 = c3f::CfgB<64, 64, 48, 6, 1, 1, true>;
+using ArmB5 = c3f::CfgB<64, 128, 24, 8, 1, 1, false>;
+using ArmB6 = c3f::CfgB<128, 128, 24, 4, 2, 2, true>;
+constexpr unsigned kArmBands = 0x1F;
 using ArmC7 = c3f::SmallCfg<128, 256, 12, 2, 5>;
 using ArmC8 = c3f::SmallCfg<256, 128, 5, 1, 3>;
 
@@ -187,11 +198,12 @@ int var_armnet_plan(var_ctx* c, int max_batch) {
     });
 }
 
-int var_armnet_forward(var_ctx* c, void* stream, const float* params, const void* image, int image_is_u8, long image_bstride,
-                       const float* image_feat, const float* robot_pose, const float* goal_sound_feat,
-                       const float* rnn_hxs, const float* masks, int B,
-                       float* value, float* actor_features, float* action_mean, float* rnn_hxs_out) {
+int var_armnet_forward_ex(var_ctx* c, void* stream, const float* params, const void* image, int image_is_u8, long image_bstride,
+                          const float* image_feat, const float* robot_pose, const float* goal_sound_feat,
+                          const float* rnn_hxs, const float* masks, int B,
+                          float* value, float* actor_features, float* action_mean, float* rnn_hxs_out, int flags) {
     if (!c) return VAR_ERR_ARG;
+    RUN(check_flags(c, "var_armnet_forward_ex", flags));
     VAR_HIP_CHECK(c, hipSetDevice(c->device));
     arm_state* st = (arm_state*)c->arm;
     if (!st || B > st->maxB) { VAR_SET_ERR(c, "var_armnet_forward: var_armnet_plan(%d) first", B); return VAR_ERR_PLAN; }
@@ -201,18 +213,21 @@ int var_armnet_forward(var_ctx* c, void* stream, const float* params, const void
     const ArmLayout& L = st->L;
     const float* P = params;
     float* slab = st->slab;
-    // imgCNN
-    if (B <= kBandMaxB) {      // conv 1 and the filter pack of conv 2..8 in one launch (c3f.h)
-        const c3f::PackDesc& d = st->pack;
-        RUN(conv1(c, s, image, image_is_u8, image_bstride, P, L.cw[0], L.cb[0], st->a[1], B, st->wpk, d));
-        RUN(c3f::launch<ArmC2>(c, s, st->a[1], st->wpk + d.wp_off[0], P + L.cb[1], st->p[1], B));
-        RUN(c3f::launch<ArmC3>(c, s, st->p[1], st->wpk + d.wp_off[1], P + L.cb[2], st->a[3], B));
-        RUN(c3f::launch<ArmC4>(c, s, st->a[3], st->wpk + d.wp_off[2], P + L.cb[3], st->p[2], B));
-        RUN(c3f::launch<ArmC5>(c, s, st->p[2], st->wpk + d.wp_off[3], P + L.cb[4], st->a[5], B));
-        RUN(c3f::launch<ArmC6>(c, s, st->a[5], st->wpk + d.wp_off[4], P + L.cb[5], st->p[3], B));
-        RUN(c3f::launch_small<ArmC7>(c, s, st->p[3], st->wpk + d.wp_off[5], P + L.cb[6], st->a[7], B));
-        RUN(c3f::launch_small<ArmC8>(c, s, st->a[7], st->wpk + d.wp_off[6], P + L.cb[7], st->a[8], B));
-    } else {
+    // imgCNN; BF (flags bit 0): every convolution multiplies operands rounded to bf16 where it stages them, everything stored stays fp32
+    auto img_cnn = [&](auto bf16) -> int {
+        constexpr bool BF = decltype(bf16)::value;
+        if (B <= kBandMaxB) {      // conv 1 and the filter pack of conv 2..8 in one launch (c3f.h)
+            const c3f::PackDesc& d = st->pack;
+            RUN(conv1(c, s, image, image_is_u8, image_bstride, P, L.cw[0], L.cb[0], st->a[1], B, st->wpk, d, BF, kArmBands));
+            RUN((band<ArmC2, ArmB2, BF>(c, s, st->a[1], st->wpk + d.wp_off[0], P + L.cb[1], st->p[1], B)));
+            RUN((band<ArmC3, ArmB3, BF>(c, s, st->p[1], st->wpk + d.wp_off[1], P + L.cb[2], st->a[3], B)));
+            RUN((band<ArmC4, ArmB4, BF>(c, s, st->a[3], st->wpk + d.wp_off[2], P + L.cb[3], st->p[2], B)));
+            RUN((band<ArmC5, ArmB5, BF>(c, s, st->p[2], st->wpk + d.wp_off[3], P + L.cb[4], st->a[5], B)));
+            RUN((band<ArmC6, ArmB6, BF>(c, s, st->a[5], st->wpk + d.wp_off[4], P + L.cb[5], st->p[3], B)));
+            RUN((c3f::launch_small<ArmC7, BF>(c, s, st->p[3], st->wpk + d.wp_off[5], P + L.cb[6], st->a[7], B)));
+            RUN((c3f::launch_small<ArmC8, BF>(c, s, st->a[7], st->wpk + d.wp_off[6], P + L.cb[7], st->a[8], B)));
+            return VAR_OK;
+        }
         using S1 = Geo<3, 3, 1, 1, 1, 1>;
         using S2P0 = Geo<3, 3, 2, 2, 0, 0>;
         using S1P0 = Geo<3, 3, 1, 1, 0, 0>;
@@ -221,19 +236,21 @@ int var_armnet_forward(var_ctx* c, void* stream, const float* params, const void
         };
         ConvDims d1 = dims(1, 96, 1, 1);
         d1.xb = image_bstride;
-        if (image_is_u8) RUN((conv<S1, true>(c, s, slab, d1, image, P + L.cw[0], P + L.cb[0], st->a[1])));
-        else RUN((conv<S1, false>(c, s, slab, d1, image, P + L.cw[0], P + L.cb[0], st->a[1])));
-        RUN((conv<S1, false>(c, s, slab, dims(2, 96, 1, 1), st->a[1], P + L.cw[1], P + L.cb[1], st->a[2])));
+        if (image_is_u8) RUN((conv<S1, true, BF>(c, s, slab, d1, image, P + L.cw[0], P + L.cb[0], st->a[1])));
+        else RUN((conv<S1, false, BF>(c, s, slab, d1, image, P + L.cw[0], P + L.cb[0], st->a[1])));
+        RUN((conv<S1, false, BF>(c, s, slab, dims(2, 96, 1, 1), st->a[1], P + L.cw[1], P + L.cb[1], st->a[2])));
         RUN(pool(c, s, st->a[2], st->p[1], B, 32, 96));
-        RUN((conv<S1, false>(c, s, slab, dims(3, 48, 1, 1), st->p[1], P + L.cw[2], P + L.cb[2], st->a[3])));
-        RUN((conv<S1, false>(c, s, slab, dims(4, 48, 1, 1), st->a[3], P + L.cw[3], P + L.cb[3], st->a[4])));
+        RUN((conv<S1, false, BF>(c, s, slab, dims(3, 48, 1, 1), st->p[1], P + L.cw[2], P + L.cb[2], st->a[3])));
+        RUN((conv<S1, false, BF>(c, s, slab, dims(4, 48, 1, 1), st->a[3], P + L.cw[3], P + L.cb[3], st->a[4])));
         RUN(pool(c, s, st->a[4], st->p[2], B, 64, 48));
-        RUN((conv<S1, false>(c, s, slab, dims(5, 24, 1, 1), st->p[2], P + L.cw[4], P + L.cb[4], st->a[5])));
-        RUN((conv<S1, false>(c, s, slab, dims(6, 24, 1, 1), st->a[5], P + L.cw[5], P + L.cb[5], st->a[6])));
+        RUN((conv<S1, false, BF>(c, s, slab, dims(5, 24, 1, 1), st->p[2], P + L.cw[4], P + L.cb[4], st->a[5])));
+        RUN((conv<S1, false, BF>(c, s, slab, dims(6, 24, 1, 1), st->a[5], P + L.cw[5], P + L.cb[5], st->a[6])));
         RUN(pool(c, s, st->a[6], st->p[3], B, 128, 24));
-        RUN((conv<S2P0, false>(c, s, slab, dims(7, 12, 2, 0), st->p[3], P + L.cw[6], P + L.cb[6], st->a[7])));
-        RUN((conv<S1P0, false>(c, s, slab, dims(8, 5, 1, 0), st->a[7], P + L.cw[7], P + L.cb[7], st->a[8])));
-    }
+        RUN((conv<S2P0, false, BF>(c, s, slab, dims(7, 12, 2, 0), st->p[3], P + L.cw[6], P + L.cb[6], st->a[7])));
+        RUN((conv<S1P0, false, BF>(c, s, slab, dims(8, 5, 1, 0), st->a[7], P + L.cw[7], P + L.cb[7], st->a[8])));
+        return VAR_OK;
+    };
+    RUN((flags & kFlagBf16) ? img_cnn(std::true_type{}) : img_cnn(std::false_type{}));
     if (B <= kChainRows)      // the RL stage's batch: everything after the convolutions in one persistent launch
         return chain_forward(c, s, st, P, image_feat, robot_pose, goal_sound_feat, rnn_hxs, masks, B, value, actor_features, action_mean,
                              rnn_hxs_out);
@@ -252,6 +269,14 @@ int var_armnet_forward(var_ctx* c, void* stream, const float* params, const void
     RUN(linear(c, s, slab, P, L.im[1], st->t1, st->t2, B, 1));                       // (B,128)
     return layer_tail(c, s, st, P, L, L.mean, kRin, kRh, st->t2, st->t3, goal_sound_feat, rnn_hxs, masks, B, value, actor_features,
                       action_mean, rnn_hxs_out);
+}
+
+int var_armnet_forward(var_ctx* c, void* stream, const float* params, const void* image, int image_is_u8, long image_bstride,
+                       const float* image_feat, const float* robot_pose, const float* goal_sound_feat,
+                       const float* rnn_hxs, const float* masks, int B,
+                       float* value, float* actor_features, float* action_mean, float* rnn_hxs_out) {
+    return var_armnet_forward_ex(c, stream, params, image, image_is_u8, image_bstride, image_feat, robot_pose, goal_sound_feat, rnn_hxs, masks,
+                                 B, value, actor_features, action_mean, rnn_hxs_out, 0);
 }
 
 int var_armnet_status(var_ctx* c, unsigned* word) { return chain_status(c, c ? (arm_state*)c->arm : nullptr, word, "var_armnet"); }

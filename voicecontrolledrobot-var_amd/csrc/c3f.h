@@ -24,6 +24,17 @@
 namespace c3f {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// bf16 operands (the acting forwards' flags bit 0, include/var_hip.h).  The band layers have a kernel of their own on the bf16
+// matrix instruction (c3f_bf16.h).  Conv 1 and the small convolutions (c1f_pack_kernel, c3s_kernel) are small: their BF variant
+// rounds x and w to bf16 (nearest, ties to even) where it stages them and multiplies the rounded values; the products of two bf16
+// values are exact in fp32, so the fp32 matrix instructions compute relu(conv(bf16(x), bf16(w)) + b) with fp32 accumulation.
+// BF = false is the fp32 code.
+template <bool BF>
+__device__ __forceinline__ float opnd(float v) {
+    if constexpr (BF) return (float)(__bf16)v;
+    else return v;
+}
+
 template <int CIN_, int COUT_, int H_, int TR_, int NCBW_, int WCB_, bool POOL_>
 struct Cfg {
     static constexpr int CIN = CIN_, COUT = COUT_, H = H_, W = H_, TR = TR_, NCBW = NCBW_, WCB = WCB_;
@@ -58,15 +69,36 @@ struct PackDesc {
     int n_layers;
     int w_off[kMaxLayers], wp_off[kMaxLayers] /* float4 units */, cin[kMaxLayers], cout[kMaxLayers], first[kMaxLayers + 1];
 };
-__device__ __forceinline__ void pack_item(const float* __restrict__ params, f32x4* __restrict__ wp, const PackDesc& d, int i) {
+// BF: the values rounded to bf16 (c3s_kernel's BF variant reads them); a layer whose bit of `bfmask` is set -- a band layer --
+// is packed in the bf16 form of c3f_bf16.h's kernel instead, 16 bytes = the A fragment of one v_mfma_f32_16x16x32_bf16, in the
+// first half of the layer's region:
+//   ((u32x4*)wp)[((cb * (CIN / 32) + kg) * 9 + tap) * 64 + lane] = bf16{ w[16 cb + (lane & 15)][32 kg + 8 (lane >> 4) + j][tap] : j = 0..7 }
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ unsigned pack_bf16(float a, float b) {      // (img_bf16.hip's idiom: v_cvt_pk_bf16_f32, nearest even)
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2));
+}
+__device__ __forceinline__ void pack_item_bf16(const float* __restrict__ params, f32x4* __restrict__ wp, const PackDesc& d, int l, int i) {
+    const int CIN = d.cin[l], KG = CIN / 32;
+    if (i >= d.cout[l] / 16 * KG * 576) return;
+    const int lane = i & 63, tap = (i >> 6) % 9, kg = (i / 576) % KG, cb = i / (576 * KG);
+    const float* q = params + d.w_off[l] + ((long)(16 * cb + (lane & 15)) * CIN + 32 * kg + 8 * (lane >> 4)) * 9 + tap;
+    ((u32x4*)wp)[d.wp_off[l] + i] = u32x4{pack_bf16(q[0], q[9]), pack_bf16(q[18], q[27]), pack_bf16(q[36], q[45]), pack_bf16(q[54], q[63])};
+}
+template <bool BF = false>
+__device__ __forceinline__ void pack_item(const float* __restrict__ params, f32x4* __restrict__ wp, const PackDesc& d, int i, unsigned bfmask = 0) {
     if (i >= d.first[d.n_layers]) return;
     int l = 0;
     while (i >= d.first[l + 1]) ++l;
     i -= d.first[l];
+    if constexpr (BF) {
+        if ((bfmask >> l) & 1) { pack_item_bf16(params, wp, d, l, i); return; }
+    }
     const int CIN = d.cin[l], KG = CIN / 16;
     const int lane = i & 63, tap = (i >> 6) % 9, kg = (i / (64 * 9)) % KG, cb = i / (64 * 9 * KG);
     const float* q = params + d.w_off[l] + ((long)(16 * cb + (lane & 15)) * CIN + 16 * kg + (lane >> 4)) * 9 + tap;
-    wp[d.wp_off[l] + i] = f32x4{q[0], q[4 * 9], q[8 * 9], q[12 * 9]};
+    wp[d.wp_off[l] + i] = f32x4{opnd<BF>(q[0]), opnd<BF>(q[4 * 9]), opnd<BF>(q[8 * 9]), opnd<BF>(q[12 * 9])};
 }
 
 // ---- conv 1 of the stack (3 -> 32, 3x3 pad 1, 96x96; u8 / 255 or float input) + the filter pack of the later layers in ONE launch:
@@ -74,10 +106,11 @@ __device__ __forceinline__ void pack_item(const float* __restrict__ params, f32x
 // place from its state_dict() layout, a per-lane table turns k = 4 j + (lane >> 4) into its (channel, tap) offset in the LDS
 // band), the rest run pack_item().  The layer is a 9.4-MB write: the point is one launch instead of two on a dependent chain.
 constexpr int C1_H = 96, C1_TR = 2, C1_PW = C1_H + 8, C1_ROWS = C1_TR + 2, C1_PLANE = C1_ROWS * C1_PW, C1_BANDS = C1_H / C1_TR;
-template <bool U8>
+template <bool U8, bool BF = false>
 __global__ void __launch_bounds__(256) c1f_pack_kernel(const void* __restrict__ image, long bstride, const float* __restrict__ params, int w_off,
-                                                      int b_off, float* __restrict__ y, int nconv, f32x4* __restrict__ wp, PackDesc d) {
-    if ((int)blockIdx.x >= nconv) { pack_item(params, wp, d, ((int)blockIdx.x - nconv) * 256 + threadIdx.x); return; }
+                                                      int b_off, float* __restrict__ y, int nconv, f32x4* __restrict__ wp, PackDesc d,
+                                                      unsigned bfmask) {
+    if ((int)blockIdx.x >= nconv) { pack_item<BF>(params, wp, d, ((int)blockIdx.x - nconv) * 256 + threadIdx.x, bfmask); return; }
     constexpr int H = C1_H, W = C1_H, PW = C1_PW, ROWS = C1_ROWS, PLANE = C1_PLANE, NPB = (C1_TR * W / 16) / 4;
     __shared__ float band[3 * PLANE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, lk = lane >> 4;
@@ -92,7 +125,7 @@ __global__ void __launch_bounds__(256) c1f_pack_kernel(const void* __restrict__ 
         const int ch = kc / 9, tap = kc - 9 * ch, dy = tap / 3, dx = tap - 3 * dy;
         off[j] = ch * PLANE + dy * PW + dx + 3;
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) { const float v = w[(16 * cb + l15) * 27 + kc]; a[cb][j] = k < 27 ? v : 0.f; }
+        for (int cb = 0; cb < 2; ++cb) { const float v = opnd<BF>(w[(16 * cb + l15) * 27 + kc]); a[cb][j] = k < 27 ? v : 0.f; }
     }
     // band: rows r0 - 1 .. r0 + TR of the three channels, zeros outside the image
     {
@@ -105,7 +138,7 @@ __global__ void __launch_bounds__(256) c1f_pack_kernel(const void* __restrict__ 
             const int ch = e / (ROWS * W), rem = e - ch * (ROWS * W), br = rem / W, col = rem - br * W;
             const int ir = r0 - 1 + br, irc = ir < 0 ? 0 : (ir >= H ? H - 1 : ir);
             const long o = (long)b * bstride + ((long)ch * H + irc) * W + col;
-            v[u] = U8 ? (float)((const uint8_t*)image)[o] / 255.f : ((const float*)image)[o];          // dataset.py:67-68
+            v[u] = opnd<BF>(U8 ? (float)((const uint8_t*)image)[o] / 255.f : ((const float*)image)[o]);          // dataset.py:67-68
         }
 #pragma unroll
         for (int u = 0; u < PER; ++u) {
@@ -334,7 +367,7 @@ struct SmallCfg {
     static_assert((HOUT - 1) * S + 3 <= HP, "taps stay inside the (padded) input");
 };
 
-template <class C>
+template <class C, bool BF = false>
 __global__ void __launch_bounds__(256) c3s_kernel(const float* __restrict__ x, const void* __restrict__ wsrc, const float* __restrict__ bias,
                                                  float* __restrict__ y, int B) {
     constexpr int CIN = C::CIN, COUT = C::COUT, HIN = C::HIN, S = C::S, HOUT = C::HOUT, NPX = C::NPX, NPB = C::NPB, KG = C::KG, PL = C::PL;
@@ -353,9 +386,9 @@ __global__ void __launch_bounds__(256) c3s_kernel(const float* __restrict__ x, c
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
                 const float* q = w + (16 * (wk + WK * g)) * 9 + tap;
-                a[g][tap] = f32x4{q[0], q[4 * 9], q[8 * 9], q[12 * 9]};
+                a[g][tap] = f32x4{opnd<BF>(q[0]), opnd<BF>(q[4 * 9]), opnd<BF>(q[8 * 9]), opnd<BF>(q[12 * 9])};
             }
-    } else {
+    } else {      // (BF: pack_item has rounded them)
         const f32x4* wa = (const f32x4*)wsrc + (size_t)cb * KG * 576 + lane;
 #pragma unroll
         for (int g = 0; g < C::KGW; ++g)
@@ -389,7 +422,7 @@ __global__ void __launch_bounds__(256) c3s_kernel(const float* __restrict__ x, c
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const int idx = 4 * e + q, ch = idx / P0, pos = idx - ch * P0, yy = pos / HIN, xx = pos - yy * HIN;
-                        lds[ch * PL + (yy + PAD) * HP + xx + PAD] = t[q];
+                        lds[ch * PL + (yy + PAD) * HP + xx + PAD] = opnd<BF>(t[q]);
                     }
                 }
             }
@@ -439,14 +472,14 @@ __global__ void __launch_bounds__(256) c3s_kernel(const float* __restrict__ x, c
     }
 }
 
-template <class C>
+template <class C, bool BF = false>
 int launch_small(var_ctx* c, hipStream_t s, const float* x, const void* wsrc, const float* bias, float* y, int B) {
     static unsigned attr = 0;      // bit d: set on device d (function attributes are per device)
     if (!(attr & var_dev_bit(c))) {
-        VAR_HIP_CHECK(c, hipFuncSetAttribute((const void*)c3s_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDSF * 4));
+        VAR_HIP_CHECK(c, hipFuncSetAttribute((const void*)c3s_kernel<C, BF>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDSF * 4));
         attr |= var_dev_bit(c);
     }
-    hipLaunchKernelGGL(c3s_kernel<C>, dim3(B * (C::COUT / 16)), dim3(256), C::LDSF * 4, s, x, wsrc, bias, y, B);
+    hipLaunchKernelGGL((c3s_kernel<C, BF>), dim3(B * (C::COUT / 16)), dim3(256), C::LDSF * 4, s, x, wsrc, bias, y, B);
     VAR_HIP_CHECK(c, hipGetLastError());
     return VAR_OK;
 }

@@ -5,10 +5,14 @@
 // up to the sampling.  Inference only.  The same three regimes as armnet.hip: up to 64 images the image stack runs on the
 // LDS-band kernels of c3f.h (filters re-packed per call inside conv 1's launch), up to 8 rows the 22 Linear layers + GRU
 // step run as one persistent launch (chain.h), larger batches take the gather-GEMM of gg.h layer by layer with the
-// parameters in place in their state_dict() layouts.  What this forward shares with armnet.hip -- the elementwise kernels, the
+// parameters in place in their state_dict() layouts.  var_ithor_policy_forward_ex's flags bit 0 runs the imgCNN convolutions on
+// operands rounded to bf16 as armnet.hip's does (conv 2..5 on c3f_bf16.h's band kernel); the occupancy convolutions stay fp32.
+// What this forward shares with armnet.hip -- the elementwise kernels, the
 // launch helpers, the workspace, the band configurations of the image stack (also ithor_reward.hip's), the per-layer path from
 // the GRU step on -- lives in actor_critic.h.
 #include <string.h>
+
+#include <type_traits>
 
 #include "gg.h"
 
@@ -244,11 +248,12 @@ int var_ithor_policy_plan(var_ctx* c, int max_batch) {
     });
 }
 
-int var_ithor_policy_forward(var_ctx* c, void* stream, const float* params, int n_actions, const void* image, int image_is_u8,
-                             long image_bstride, const void* occupancy, int occupancy_is_u8, const float* image_feat,
-                             const float* goal_sound_feat, const float* rnn_hxs, const float* masks, int B, float* value,
-                             float* actor_features, float* logits, float* rnn_hxs_out) {
+int var_ithor_policy_forward_ex(var_ctx* c, void* stream, const float* params, int n_actions, const void* image, int image_is_u8,
+                                long image_bstride, const void* occupancy, int occupancy_is_u8, const float* image_feat,
+                                const float* goal_sound_feat, const float* rnn_hxs, const float* masks, int B, float* value,
+                                float* actor_features, float* logits, float* rnn_hxs_out, int flags) {
     if (!c) return VAR_ERR_ARG;
+    RUN(check_flags(c, "var_ithor_policy_forward_ex", flags));
     VAR_HIP_CHECK(c, hipSetDevice(c->device));
     pol_state* st = (pol_state*)c->ipol;
     if (!st || B > st->maxB) { VAR_SET_ERR(c, "var_ithor_policy_forward: var_ithor_policy_plan(%d) first", B); return VAR_ERR_PLAN; }
@@ -267,33 +272,39 @@ int var_ithor_policy_forward(var_ctx* c, void* stream, const float* params, int 
     if (occupancy_is_u8) hipLaunchKernelGGL(ip_occ_kernel<true>, dim3(B * (32 / kOccCo)), dim3(kOccT), 0, s, occupancy, P, L.ow[0], L.ob[0], L.ow[1], L.ob[1], st->occf);
     else hipLaunchKernelGGL(ip_occ_kernel<false>, dim3(B * (32 / kOccCo)), dim3(kOccT), 0, s, occupancy, P, L.ow[0], L.ob[0], L.ow[1], L.ob[1], st->occf);
     AC_CHECK(c);
-    // imgCNN
-    if (B <= kBandMaxB) {      // conv 1 and the filter pack of conv 2..6 in one launch (c3f.h)
-        const c3f::PackDesc& d = st->pack;
-        RUN(conv1(c, s, image, image_is_u8, image_bstride, P, L.cw[0], L.cb[0], st->a[1], B, st->wpk, d));
-        RUN(c3f::launch<IthorC2>(c, s, st->a[1], st->wpk + d.wp_off[0], P + L.cb[1], st->p[1], B));
-        RUN(c3f::launch<IthorC3>(c, s, st->p[1], st->wpk + d.wp_off[1], P + L.cb[2], st->p[2], B));
-        RUN(c3f::launch<IthorC4>(c, s, st->p[2], st->wpk + d.wp_off[2], P + L.cb[3], st->p[3], B));
-        RUN(c3f::launch<IthorC5>(c, s, st->p[3], st->wpk + d.wp_off[3], P + L.cb[4], st->p[4], B));
-        RUN(c3f::launch_small<IthorC6>(c, s, st->p[4], st->wpk + d.wp_off[4], P + L.cb[5], st->a[6], B));
-    } else {
+    // imgCNN; BF (flags bit 0): every convolution multiplies operands rounded to bf16 where it stages them, everything stored stays
+    // fp32 (the occupancy convolutions above stay fp32)
+    auto img_cnn = [&](auto bf16) -> int {
+        constexpr bool BF = decltype(bf16)::value;
+        if (B <= kBandMaxB) {      // conv 1 and the filter pack of conv 2..6 in one launch (c3f.h)
+            const c3f::PackDesc& d = st->pack;
+            RUN(conv1(c, s, image, image_is_u8, image_bstride, P, L.cw[0], L.cb[0], st->a[1], B, st->wpk, d, BF, kIthorBands));
+            RUN((band<IthorC2, IthorB2, BF>(c, s, st->a[1], st->wpk + d.wp_off[0], P + L.cb[1], st->p[1], B)));
+            RUN((band<IthorC3, IthorB3, BF>(c, s, st->p[1], st->wpk + d.wp_off[1], P + L.cb[2], st->p[2], B)));
+            RUN((band<IthorC4, IthorB4, BF>(c, s, st->p[2], st->wpk + d.wp_off[2], P + L.cb[3], st->p[3], B)));
+            RUN((band<IthorC5, IthorB5, BF>(c, s, st->p[3], st->wpk + d.wp_off[3], P + L.cb[4], st->p[4], B)));
+            RUN((c3f::launch_small<IthorC6, BF>(c, s, st->p[4], st->wpk + d.wp_off[4], P + L.cb[5], st->a[6], B)));
+            return VAR_OK;
+        }
         using S1 = Geo<3, 3, 1, 1, 1, 1>;
         using S2P1 = Geo<3, 3, 2, 2, 1, 1>;
         auto dims = [&](int l, int hin, int stride) { return conv_dims(B, kCh[l - 1], hin, hin, kCh[l], 3, 3, stride, stride, 1, 1); };
         ConvDims d1 = dims(1, 96, 1);
         d1.xb = image_bstride;
-        if (image_is_u8) RUN((conv<S1, true>(c, s, slab, d1, image, P + L.cw[0], P + L.cb[0], st->a[1])));
-        else RUN((conv<S1, false>(c, s, slab, d1, image, P + L.cw[0], P + L.cb[0], st->a[1])));
-        RUN((conv<S1, false>(c, s, slab, dims(2, 96, 1), st->a[1], P + L.cw[1], P + L.cb[1], st->a[2])));
+        if (image_is_u8) RUN((conv<S1, true, BF>(c, s, slab, d1, image, P + L.cw[0], P + L.cb[0], st->a[1])));
+        else RUN((conv<S1, false, BF>(c, s, slab, d1, image, P + L.cw[0], P + L.cb[0], st->a[1])));
+        RUN((conv<S1, false, BF>(c, s, slab, dims(2, 96, 1), st->a[1], P + L.cw[1], P + L.cb[1], st->a[2])));
         RUN(pool(c, s, st->a[2], st->p[1], B, 32, 96));
-        RUN((conv<S1, false>(c, s, slab, dims(3, 48, 1), st->p[1], P + L.cw[2], P + L.cb[2], st->a[3])));
+        RUN((conv<S1, false, BF>(c, s, slab, dims(3, 48, 1), st->p[1], P + L.cw[2], P + L.cb[2], st->a[3])));
         RUN(pool(c, s, st->a[3], st->p[2], B, 64, 48));
-        RUN((conv<S1, false>(c, s, slab, dims(4, 24, 1), st->p[2], P + L.cw[3], P + L.cb[3], st->a[4])));
+        RUN((conv<S1, false, BF>(c, s, slab, dims(4, 24, 1), st->p[2], P + L.cw[3], P + L.cb[3], st->a[4])));
         RUN(pool(c, s, st->a[4], st->p[3], B, 64, 24));
-        RUN((conv<S1, false>(c, s, slab, dims(5, 12, 1), st->p[3], P + L.cw[4], P + L.cb[4], st->a[5])));
+        RUN((conv<S1, false, BF>(c, s, slab, dims(5, 12, 1), st->p[3], P + L.cw[4], P + L.cb[4], st->a[5])));
         RUN(pool(c, s, st->a[5], st->p[4], B, 128, 12));
-        RUN((conv<S2P1, false>(c, s, slab, dims(6, 6, 2), st->p[4], P + L.cw[5], P + L.cb[5], st->a[6])));
-    }
+        RUN((conv<S2P1, false, BF>(c, s, slab, dims(6, 6, 2), st->p[4], P + L.cw[5], P + L.cb[5], st->a[6])));
+        return VAR_OK;
+    };
+    RUN((flags & kFlagBf16) ? img_cnn(std::true_type{}) : img_cnn(std::false_type{}));
     if (B <= kChainRows)      // the RL stage's batch: everything after the convolutions in one persistent launch
         return chain_forward(c, s, st, P, image_feat, goal_sound_feat, rnn_hxs, masks, B, value, actor_features, logits, rnn_hxs_out);
     // B > 8 rows: one launch per Linear layer (+ the sums, the mask and the GRU cell)
@@ -311,6 +322,14 @@ int var_ithor_policy_forward(var_ctx* c, void* stream, const float* params, int 
     RUN(linear(c, s, slab, P, L.im[1], st->t0, st->t2, B, 1));                       // (B,128)
     return layer_tail(c, s, st, P, L, L.logit, kRin, kRh, st->t2, st->h1, goal_sound_feat, rnn_hxs, masks, B, value, actor_features, logits,
                       rnn_hxs_out);
+}
+
+int var_ithor_policy_forward(var_ctx* c, void* stream, const float* params, int n_actions, const void* image, int image_is_u8,
+                             long image_bstride, const void* occupancy, int occupancy_is_u8, const float* image_feat,
+                             const float* goal_sound_feat, const float* rnn_hxs, const float* masks, int B, float* value,
+                             float* actor_features, float* logits, float* rnn_hxs_out) {
+    return var_ithor_policy_forward_ex(c, stream, params, n_actions, image, image_is_u8, image_bstride, occupancy, occupancy_is_u8, image_feat,
+                                       goal_sound_feat, rnn_hxs, masks, B, value, actor_features, logits, rnn_hxs_out, 0);
 }
 
 int var_ithor_policy_status(var_ctx* c, unsigned* word) { return chain_status(c, c ? (pol_state*)c->ipol : nullptr, word, "var_ithor_policy"); }
