@@ -770,7 +770,15 @@ int var_mfcc_psf(var_ctx* ctx, void* stream, const int16_t* pcm, const int* lens
  * such failure mode, so it is reported).
  * var_debug_buffer: address/length of a named workspace buffer ("act1".."act5", "gact1"..,
  * "sact1".."sact4", "gsact1".., "emb", "gemb", "wpack"; "ithor_s1".."ithor_s3", "ithor_gs1".."ithor_gs3") for
- * layer-wise parity tests.  The iTHOR model's names, after the "ithor_" prefix (lengths are those of the PLAN's batch; the
+ * layer-wise parity tests.  The Kuka heads' rows: "hid_i" (B, 128) and "hid_s" (positive clips from row 0, negative ones
+ * from row B, 128 floats each); the others are (3 maxB) stacks [image | positive | negative] that a call of B samples fills
+ * with B-BASED offsets (image rows from row 0, positive clips from row B, negative ones from row 2B): "emb" / "emb_raw" (rows
+ * of 3: the normalised and the un-normalised embeddings), "head_part" (rows of 16: the four partial sums of the 128 -> 3
+ * layer, 4 floats each, the fourth unused; img_mid3 leaves an image's whole sum in the first group), "gemb" (rows of 3),
+ * "graw" (rows of 4: the gradient wrt emb_raw and a zero) and "ghid" (rows of 128: the masked hidden gradient); graw and
+ * ghid are written by var_arm_encoder_bwd and by the training step above 1024 rows per head -- below that the fused step
+ * forms them in registers only.
+ * The iTHOR model's names, after the "ithor_" prefix (lengths are those of the PLAN's batch; the
  * saved forward fills the first B images | nclips clips of each, sound-side strides by nclips): a1..a6, p2..p5, ga1..ga6,
  * gp2..gp5 (image maps, pooled maps, gradients), s1..s3, gs1..gs3 (sound maps; 3 in the (clip, 73, 64, 7) sequence layout),
  * gi (dir, clip*73 + t, 1536), hb (dir, step 0..73, clip, 512), gh (split-K partials), dgi (as gi), dgh (dir, step, clip,

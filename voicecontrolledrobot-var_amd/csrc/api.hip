@@ -766,7 +766,8 @@ int var_profile_read(var_ctx* c, float* total_ms, int* count) {
 }
 
 /* Testing hook: address and length (floats) of a workspace buffer, by name
- * ("act1".."act5", "gact1".."gact5", "sact1".."sact4", "gsact1".."gsact4", "emb", "gemb", "wpack";
+ * ("act1".."act5", "gact1".."gact5", "sact1".."sact4", "gsact1".."gsact4", "emb", "gemb", "wpack", the heads' rows
+ * "emb_raw", "head_part", "graw", "ghid";
  * iTHOR workspace: "ithor_s1".."ithor_s3", "ithor_gs1".."ithor_gs3": sound conv outputs / their gradients, sized for
  * the planned batch; the acting forwards' workspaces: "arm_..." (armnet.hip), "ipol_..." (ithor_policy.hip), names in
  * include/var_hip.h). */
@@ -809,6 +810,11 @@ int var_debug_buffer(var_ctx* c, const char* name, void** ptr, long* nfloats) {
     if (!strcmp(name, "mfcc")) { *ptr = c->mfcc_buf; *nfloats = 2 * (long)B * VAR_MFCC_FRAMES * VAR_MFCC_COEFFS; return VAR_OK; }
     if (!strcmp(name, "slabs")) { *ptr = c->slabs; *nfloats = (long)c->slab_floats; return VAR_OK; }
     if (!strcmp(name, "gemb")) { *ptr = c->gemb; *nfloats = 9 * (long)B; return VAR_OK; }
+    // the heads' rows, all (3 maxB) stacks [image | positive | negative] filled with B-based offsets (heads.hip)
+    if (!strcmp(name, "emb_raw")) { *ptr = c->emb_raw; *nfloats = 9 * (long)B; return VAR_OK; }
+    if (!strcmp(name, "head_part")) { *ptr = c->head_part; *nfloats = 48 * (long)B; return VAR_OK; }
+    if (!strcmp(name, "graw")) { *ptr = c->gemb + 9 * B; *nfloats = 12 * (long)B; return VAR_OK; }
+    if (!strcmp(name, "ghid")) { *ptr = c->ghid; *nfloats = 3 * (long)B * kHid; return VAR_OK; }
     VAR_SET_ERR(c, "var_debug_buffer: unknown buffer '%s'", name);
     return VAR_ERR_ARG;
 }
