@@ -543,6 +543,62 @@ int var_ppo_head(var_ctx* ctx, void* stream, int kind /*0 DiagGaussian, 1 Catego
                  int use_clipped_value_loss, float* out /* 4 */, float* g_head, float* g_value, float* g_logstd,
                  float* logp /* (M,1), may be NULL */);
 
+/* The env wrapper's step on the device: reward, normaliser, insert ----------------------------------------------------------
+ * What VecPretextNormalize.step_wait and calcReward do on the host between the simulator's return and the next act
+ * (Envs/vec_env/vec_pretext_normalize.py:47-61, 96-101) and what RL.py:171-185 does with the result, as two entries of ONE
+ * launch each whose arguments do not change from step to step: a captured graph replays them (csrc/env_step.hip).  Neither
+ * entry waits for another workgroup, allocates or synchronises; there is no time-out and no status word.
+ *
+ * var_reward_norm_step: one workgroup, float64, each operation rounded once in the reference's grouping.  Inputs, device:
+ * dot (N) f32 or NULL (= 0): <image_feat, goal_sound_feat>; env_reward (N) f64; done (N) u8; bad (N) u8 or NULL (no
+ * 'bad_transition').  normalise = 0 is the wrapper built with ret=False.  State, device float64: ret (N), rms[3] = {mean, var,
+ * count} of running_mean_std.py:4-35 (a fresh one is {0, 1, 1e-4}), episode (3N) = the running sum of the un-normalised step
+ * reward, the sum of the last finished episode, the number of finished episodes per env (RL.py:171-176: the host reads it when it
+ * logs), slot int32[2].  Outputs: reward, masks, bad_masks (N,1) f32, orig_reward (N) f64 (origStepReward, :53).  Per env i:
+ *     rews = (double)dot[i] + env_reward[i]                                      (calcReward, :96-101; RLRewardSoundSound off)
+ *     ret[i] = ret[i] * gamma + rews                                                                                      (:55)
+ *     normalise: bm = mean_i ret, bv = mean_i (ret - bm) * (ret - bm); delta = bm - mean; total = count + N;
+ *         m2 = (var * count + bv * N) + (((delta * delta) * count) * N) / total;
+ *         mean = mean + (delta * N) / total; var = m2 / total; count = total                (running_mean_std.py:22-32)
+ *         rews = clip(rews / sqrt(var + epsilon), -cliprew, cliprew)                              (:58; a NaN stays a NaN)
+ *     reward[i] = (float)rews;  masks[i] = done[i] ? 0 : 1;  bad_masks[i] = bad && bad[i] ? 0 : 1       (RL.py:179-183)
+ *     ret[i] = 0 where done[i]                                                                                            (:59)
+ *     episode: run = episode[i] + (un-normalised rews); where done[i]: episode[N+i] = run, episode[2N+i] += 1, run = 0;
+ *         episode[i] = run
+ * The two sums over the envs are taken by one thread in numpy's order (np.add.reduce of a contiguous float64 vector of at
+ * most 128 elements): N < 8 left to right; else eight running sums over blocks of eight, folded ((r0+r1)+(r2+r3))+((r4+r5)+
+ * (r6+r7)), then the remaining N % 8 elements one by one -- the state equals the reference's numpy bit for bit.
+ * slot: the kernel stores slot[1] = slot[0], then slot[0] = (slot[0] + 1) % num_steps: slot[1] is the rollout step this env
+ * step's insert writes to, carried on the device so that the launch after it (var_rollout_move_at, given &slot[1]) needs no
+ * host-computed address.
+ * VAR_ERR_ARG: N < 1 or N > 128 (numpy's pairwise recursion starts there), num_steps < 1, a NULL pointer other than dot / bad,
+ * an output or state range overlapping an input or another output.  A failed call launches nothing.
+ *
+ * var_rollout_move_at: var_rollout_move (same piece widths, same kernel body) without an index list, n_src_env = n_env, whose
+ * destinations a device word selects: `segs` is a HOST array of 1..VAR_MOVE_MAX_SEGS entries (it travels by value), `slot` a
+ * DEVICE pointer of which the kernel reads slot[0].  Segment k goes to seg.dst + (slot[0] + slot_add) * dst_slot_stride
+ * (bytes), and is left unwritten when slot[0] + slot_add lies outside [0, n_slots) (the word lives on the device: the host
+ * cannot refuse it).  dst_slot_stride = 0 makes the segment a plain copy: the word is not consulted and n_slots must be 1.
+ * RolloutStorage.insert (storage.py:61-77) is slot_add = 1, n_slots = T + 1 for obs, hidden states, masks, bad_masks and slot_add =
+ * 0, n_slots = T for actions, log-probs, value_preds, rewards, each seg.dst the store's slot 0 and dst_slot_stride one slot.
+ * The piece width also has to divide dst_slot_stride.
+ * VAR_ERR_ARG: everything var_rollout_move refuses of a segment; slot NULL, n_env < 1, dst_slot_stride < 0, n_slots < 1,
+ * 0 < dst_slot_stride < one slot's rows; the overlap checks run over a segment's WHOLE slot range (first byte of slot 0 to last
+ * byte of slot n_slots - 1) against every source range, every other destination range and the slot word.  A failed call
+ * launches nothing. */
+typedef struct var_move_at_seg {
+    var_move_seg seg;
+    long dst_slot_stride;
+    int slot_add, n_slots;
+} var_move_at_seg;
+int var_reward_norm_step(var_ctx* ctx, void* stream, const float* dot /* (N) | NULL */, const double* env_reward,
+                         const unsigned char* done, const unsigned char* bad /* (N) | NULL */, int N, double gamma,
+                         double cliprew, double epsilon, int normalise, int num_steps, double* ret, double* rms /* 3 */,
+                         double* episode /* 3N */, int* slot /* 2 */, float* reward, float* masks, float* bad_masks,
+                         double* orig_reward);
+int var_rollout_move_at(var_ctx* ctx, void* stream, const var_move_at_seg* segs /* host */, int n_seg,
+                        const int* slot /* device */, int n_env);
+
 /* The PPO update's recurrent sequence, forward and backward --------------------------------------------------------------
  * NNBase._forward_gru (models/ppo/model.py:116-171) of a one-layer, one-direction nn.GRU with biases, as PPO.update
  * (models/ppo/algo/ppo.py:55-58 -> Policy.evaluate_actions, model.py:75-83) runs it on every minibatch: x (T*N, I), hxs (N, H),

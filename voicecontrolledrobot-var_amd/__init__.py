@@ -18,6 +18,7 @@ from .data import SyntheticTripletPool, TripletPool, choose_negative_id, load_wa
 from .ops import inbatch_contrastive_loss, mfcc, mfcc_psf, triplet_margin_loss  # noqa: F401
 from .reward import IntrinsicReward, ReturnNormalizer, RunningMeanStd  # noqa: F401
 from .rollout import PPO, RolloutStorage, ppo_loss  # noqa: F401
+from .collect import CollectStep, DeviceReturnNormalizer  # noqa: F401
 from .gru_seq import bind_forward_gru, forward_gru, masked_gru  # noqa: F401
 from .trunk import bind_trunk, trunk_eval  # noqa: F401
 from .convstack import bind_convs, conv_stack_eval  # noqa: F401

@@ -38,6 +38,11 @@ class MoveSeg(ctypes.Structure):
                 ("src_env_stride", _l), ("dst_env_stride", _l)]
 
 
+class MoveAtSeg(ctypes.Structure):
+    """var_move_at_seg of include/var_hip.h (var_rollout_move_at's segment table, a host array)."""
+    _fields_ = [("seg", MoveSeg), ("dst_slot_stride", _l), ("slot_add", _i), ("n_slots", _i)]
+
+
 class OptSeg(ctypes.Structure):
     """var_opt_seg of include/var_hip.h (var_clip_adam_step's segment table, a host array)."""
     _fields_ = [("p", _vp), ("g", _vp), ("m", _vp), ("v", _vp), ("n", _l)]
@@ -95,6 +100,8 @@ _SIGNATURES = {
     "var_rollout_move": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i]),
     "var_rollout_returns": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _d, _d, _i, _vp, _vp]),
     "var_ppo_head": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _l, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+    "var_reward_norm_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _d, _d, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "var_rollout_move_at": (_i, [_vp, _vp, _vp, _i, _vp, _i]),
     "var_gru_seq_workspace_bytes": (_l, [_i, _i, _i, _i]),
     "var_gru_seq_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _l]),
     "var_gru_seq_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l]),

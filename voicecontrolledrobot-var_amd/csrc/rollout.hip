@@ -5,10 +5,11 @@
 // Latency work: each replaces tens to hundreds of torch launches on (N,1) / (T*N,1) tensors.  fp32, no product is contracted
 // into an fma (-ffp-contract=off): the recurrences below round where the reference's torch expressions round.
 #include "var_common.h"
+#include "rollout_move.h"
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = var_move::kThreads;
 
 // Sum over the workgroup in a fixed order: butterfly inside each wave, then the four wave sums in index order.  Every thread
 // returns the same value; two calls may follow each other (the barrier at the top protects the previous call's reads).
@@ -22,53 +23,13 @@ __device__ __forceinline__ float block_sum(float v, float* sm4) {
 }
 
 // ---- var_rollout_move -----------------------------------------------------------------------------------------------------
-// A row is cut into 16-byte pieces, one per thread.  Rows of 256 pieces or more take ceil(pieces / 256) workgroups each; shorter
-// rows share a workgroup (256 / pieces of them).  gran: what both ends, the length and every stride are multiples of -- 16: one
-// 16-byte load and store per piece, 4: up to four words, 1: up to sixteen bytes.
-struct MoveSeg {
-    const char* src; char* dst;
-    long row_bytes, st, dt, se, de;     // strides in bytes: time (src, dst), env (src, dst)
-    long rows;                          // n_t * n_env
-    int ppr, rpb, cpr, gran;            // pieces per row, rows per workgroup, workgroups per row (one of rpb / cpr is 1)
-    unsigned blk0;                      // first workgroup of this segment
-};
-struct MoveTable { MoveSeg s[VAR_MOVE_MAX_SEGS]; int n; };
+// The piece copy, the segment table and its host-side planning live in rollout_move.h (var_rollout_move_at shares them).
+using var_move::MoveTable;
+using var_move::overlap;
 
 __global__ void __launch_bounds__(kThreads) rollout_move_kernel(MoveTable tab, const int* __restrict__ ind, int n_env, int n_src_env) {
     const unsigned b = blockIdx.x;
-    int si = 0;
-#pragma unroll
-    for (int i = 1; i < VAR_MOVE_MAX_SEGS; ++i) si += (i < tab.n && b >= tab.s[i].blk0) ? 1 : 0;
-    const MoveSeg& sg = tab.s[si];
-    const long lb = (long)(b - sg.blk0);
-    const int tid = threadIdx.x;
-    long row, piece;
-    if (sg.cpr > 1) { row = lb / sg.cpr; piece = (lb % sg.cpr) * kThreads + tid; }
-    else            { const int rl = tid / sg.ppr; row = lb * sg.rpb + rl; piece = tid % sg.ppr; if (rl >= sg.rpb) return; }
-    if (row >= sg.rows || piece >= sg.ppr) return;
-    const long t = row / n_env, j = row % n_env;
-    const long e = ind ? (long)ind[j] : j;
-    if (e < 0 || e >= n_src_env) return;                        // an index outside the source: that row is left alone
-    const long off = piece * 16, left = sg.row_bytes - off;     // left >= 1
-    const char* s = sg.src + t * sg.st + e * sg.se + off;
-    char* d = sg.dst + t * sg.dt + j * sg.de + off;
-    if (sg.gran == 16) {
-        *(uint4*)d = *(const uint4*)s;
-    } else if (sg.gran == 4) {
-        const int nw = left >= 16 ? 4 : (int)(left >> 2);
-        unsigned w[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) if (k < nw) w[k] = ((const unsigned*)s)[k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) if (k < nw) ((unsigned*)d)[k] = w[k];
-    } else {
-        const int nb = left >= 16 ? 16 : (int)left;
-        unsigned char w[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) if (k < nb) w[k] = ((const unsigned char*)s)[k];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) if (k < nb) ((unsigned char*)d)[k] = w[k];
-    }
+    var_move::move_piece(tab.s[var_move::move_segment_of(tab, b)], b, ind, n_env, n_src_env, 0);
 }
 
 // ---- var_rollout_returns --------------------------------------------------------------------------------------------------
@@ -277,11 +238,6 @@ __global__ void __launch_bounds__(kThreads) ppo_head_kernel(const float* __restr
     out[3] = (vl * vcoef + al) - ent * ecoef;
 }
 
-inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const char *p = (const char*)a, *q = (const char*)b;
-    return p < q + nb && q < p + na;
-}
-
 }  // namespace
 
 extern "C" int var_rollout_move(var_ctx* c, void* stream, const var_move_seg* segs, int n_seg, const int* ind, int n_env,
@@ -300,35 +256,8 @@ extern "C" int var_rollout_move(var_ctx* c, void* stream, const var_move_seg* se
     size_t sext[VAR_MOVE_MAX_SEGS], dext[VAR_MOVE_MAX_SEGS];
     unsigned long long blocks = 0;
     for (int i = 0; i < n_seg; ++i) {
-        const var_move_seg& u = segs[i];
-        if (!u.src || !u.dst || u.row_bytes < 1 || u.n_t < 1 || u.src_t_stride < 0 || u.dst_t_stride < 0 || u.src_env_stride < 0 ||
-            u.dst_env_stride < 0 || u.n_t > (1L << 31) || u.row_bytes > (1L << 40)) {
-            VAR_SET_ERR(c, "var_rollout_move: segment %d: NULL end, row_bytes / n_t < 1 or a negative stride", i);
-            return VAR_ERR_ARG;
-        }
-        // destination rows in their natural order: an env's row ends before the next one's starts, a step's rows before the next step's
-        if ((n_env > 1 && u.dst_env_stride < u.row_bytes) ||
-            (u.n_t > 1 && u.dst_t_stride < (long)(n_env - 1) * u.dst_env_stride + u.row_bytes)) {
-            VAR_SET_ERR(c, "var_rollout_move: segment %d: destination rows overlap each other", i);
-            return VAR_ERR_ARG;
-        }
-        sext[i] = (size_t)((u.n_t - 1) * u.src_t_stride + (long)(n_src_env - 1) * u.src_env_stride + u.row_bytes);
-        dext[i] = (size_t)((u.n_t - 1) * u.dst_t_stride + (long)(n_env - 1) * u.dst_env_stride + u.row_bytes);
-        MoveSeg& g = tab.s[i];
-        g.src = (const char*)u.src; g.dst = (char*)u.dst;
-        g.row_bytes = u.row_bytes; g.st = u.src_t_stride; g.dt = u.dst_t_stride; g.se = u.src_env_stride; g.de = u.dst_env_stride;
-        g.rows = u.n_t * (long)n_env;
-        const unsigned long long bits = (uintptr_t)u.src | (uintptr_t)u.dst | (unsigned long long)u.row_bytes | (unsigned long long)u.src_t_stride |
-                                        (unsigned long long)u.dst_t_stride | (unsigned long long)u.src_env_stride | (unsigned long long)u.dst_env_stride;
-        g.gran = (bits & 15) == 0 ? 16 : ((bits & 3) == 0 ? 4 : 1);
-        const long ppr = (u.row_bytes + 15) / 16;
-        g.ppr = (int)(ppr < (1L << 30) ? ppr : (1L << 30));
-        if (ppr >= (1L << 30)) { VAR_SET_ERR(c, "var_rollout_move: segment %d: row too long", i); return VAR_ERR_ARG; }
-        if (ppr >= kThreads) { g.cpr = (int)((ppr + kThreads - 1) / kThreads); g.rpb = 1; }
-        else                 { g.cpr = 1; g.rpb = kThreads / (int)ppr; }
-        g.blk0 = (unsigned)blocks;
-        blocks += g.cpr > 1 ? (unsigned long long)g.rows * g.cpr : (unsigned long long)((g.rows + g.rpb - 1) / g.rpb);
-        if (blocks > 0x7fffffffull) { VAR_SET_ERR(c, "var_rollout_move: more than 2^31 - 1 workgroups"); return VAR_ERR_ARG; }
+        const int rc = var_move::move_plan_seg(c, "var_rollout_move", i, segs[i], n_env, n_src_env, 0, tab.s[i], blocks, sext[i], dext[i]);
+        if (rc != VAR_OK) return rc;
     }
     for (int i = 0; i < n_seg; ++i) {
         for (int j = 0; j < n_seg; ++j) {
