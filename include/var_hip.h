@@ -599,6 +599,54 @@ int var_reward_norm_step(var_ctx* ctx, void* stream, const float* dot /* (N) | N
 int var_rollout_move_at(var_ctx* ctx, void* stream, const var_move_at_seg* segs /* host */, int n_seg,
                         const int* slot /* device */, int n_env);
 
+/* A PPO minibatch step without the host: the head's Linear fused with the loss, a gather behind a cursor ----------------------
+ * The two entries that let one captured sequence serve every minibatch of an update (csrc/ppo_step.hip).  Neither waits for
+ * another workgroup, allocates or synchronises; neither uses a floating-point atomic.
+ *
+ * var_ppo_head_linear: dist.fc_mean / dist.linear (models/ppo/distributions.py) and var_ppo_head in one call of two launches.
+ *   head (M,n) = features (M,128) . W^T + b, W (n,128) and b (n) in nn.Linear's layout; head is an output;
+ *   out[4], g_value (M,1), g_logstd (n, kind 0): var_ppo_head's, computed on that head by var_ppo_head's own device code
+ *       (csrc/ppo_row.h) in var_ppo_head's row -> thread -> workgroup layout: fed the returned head, var_ppo_head gives the
+ *       same bits.  kind / n / the loss's inputs, formulas and kinks: see var_ppo_head;
+ *   g_features (M,128) = g_head . W,  g_W (n,128) = g_head^T . features,  g_b (n) = sum over the rows of g_head, g_head being
+ *       var_ppo_head's d total / d head (it is not written out).
+ * Summation orders depend on (M, n) only, so equal inputs give equal bits: a head value is 8 partial dot products (lane p of
+ * the row takes the 16-byte pieces p, p + 8, p + 16, p + 24, left to right) joined by a butterfly, plus b; a g_features value
+ * runs over k = 0 .. n-1; g_W / g_b are summed per workgroup (rows grid-strided in rounds of 256 over at most 256 workgroups;
+ * inside one, eight row slices r % 8, each in row order, added in index order) and the workgroups' partials are added in index
+ * order by the second launch, which also folds the loss sums as var_ppo_head does.  The partials live in `workspace`:
+ * var_ppo_head_linear_workspace_bytes(kind, n, M) bytes (VAR_ERR_ARG for a refused shape), 16-byte aligned, contents
+ * irrelevant before and after.  M is not bounded.  Concurrent calls need distinct workspaces, nothing else.
+ * stats / cursor (device, both or neither): stats holds n_stats_rows rows of {value_loss, action_loss, dist_entropy}, cursor is
+ * int32[2].  The launch that writes out[4] then also writes the three losses to stats row cursor[1] -- a row index outside
+ * [0, n_stats_rows) leaves stats unwritten (the word lives on the device: the host cannot refuse it) -- and then adds n_env to
+ * cursor[0] and 1 to cursor[1]: cursor[0] is what var_rollout_move_cursor reads, and stream order puts this behind the gather
+ * that read it.
+ * VAR_ERR_ARG: everything var_ppo_head refuses; NULL features / W / b / head / g_features / g_W / g_b / workspace; a workspace
+ * shorter than the query's bytes or not 16-byte aligned; features or g_features not 16-byte aligned (W may lie at any word); one of stats / cursor
+ * without the other, n_stats_rows < 1 or n_env < 0 with them; an output (head, out, g_features, g_W, g_b, g_value, g_logstd,
+ * workspace, stats, cursor) overlapping an input or another output.  A failed call launches nothing.
+ *
+ * var_rollout_move_cursor: var_rollout_move (same piece widths, same kernel body, same refusals) whose index list is
+ * ind_base + cursor[0]: ind_base a DEVICE int32 list of n_ind entries, cursor a DEVICE pointer of which the kernel reads
+ * cursor[0].  When cursor[0] < 0 or cursor[0] + n_env > n_ind nothing is written (the word lives on the device: the host
+ * cannot refuse it).  With all minibatches' env lists of an update behind ind_base and var_ppo_head_linear advancing the
+ * cursor, one captured launch gathers every minibatch.
+ * VAR_ERR_ARG: everything var_rollout_move refuses; ind_base or cursor NULL, n_ind < 1, n_env > n_ind; a destination range that
+ * holds the cursor word or overlaps the index list.  A failed call launches nothing. */
+long var_ppo_head_linear_workspace_bytes(int kind, int n, long M);
+int var_ppo_head_linear(var_ctx* ctx, void* stream, int kind /*0 DiagGaussian, 1 Categorical*/, const float* features /* (M,128) */,
+                        const float* W /* (n,128) */, const float* b /* (n) */, const float* logstd, const float* value,
+                        const void* action, const float* old_logp, const float* adv, const float* returns,
+                        const float* value_preds, int n, long M, float clip, float value_coef, float entropy_coef,
+                        int use_clipped_value_loss, float* head /* (M,n) */, float* out /* 4 */, float* g_features /* (M,128) */,
+                        float* g_W /* (n,128) */, float* g_b /* (n) */, float* g_value, float* g_logstd, void* workspace,
+                        long workspace_bytes, float* stats /* (n_stats_rows,3) | NULL */, int n_stats_rows,
+                        int* cursor /* 2, device | NULL */, int n_env);
+int var_rollout_move_cursor(var_ctx* ctx, void* stream, const var_move_seg* segs /* host */, int n_seg,
+                            const int* ind_base /* device (n_ind) */, int n_ind, const int* cursor /* device */, int n_env,
+                            int n_src_env);
+
 /* The PPO update's recurrent sequence, forward and backward --------------------------------------------------------------
  * NNBase._forward_gru (models/ppo/model.py:116-171) of a one-layer, one-direction nn.GRU with biases, as PPO.update
  * (models/ppo/algo/ppo.py:55-58 -> Policy.evaluate_actions, model.py:75-83) runs it on every minibatch: x (T*N, I), hxs (N, H),

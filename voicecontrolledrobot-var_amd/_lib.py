@@ -102,6 +102,10 @@ _SIGNATURES = {
     "var_ppo_head": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _l, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "var_reward_norm_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _d, _d, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "var_rollout_move_at": (_i, [_vp, _vp, _vp, _i, _vp, _i]),
+    "var_ppo_head_linear_workspace_bytes": (_l, [_i, _i, _l]),
+    "var_ppo_head_linear": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _l, _f, _f, _f, _i, _vp, _vp, _vp,
+                                 _vp, _vp, _vp, _vp, _vp, _l, _vp, _i, _vp, _i]),
+    "var_rollout_move_cursor": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i]),
     "var_gru_seq_workspace_bytes": (_l, [_i, _i, _i, _i]),
     "var_gru_seq_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _l]),
     "var_gru_seq_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l]),

@@ -6,26 +6,18 @@
 // into an fma (-ffp-contract=off): the recurrences below round where the reference's torch expressions round.
 #include "var_common.h"
 #include "rollout_move.h"
+#include "ppo_row.h"
 
 namespace {
 
 constexpr int kThreads = var_move::kThreads;
 
-// Sum over the workgroup in a fixed order: butterfly inside each wave, then the four wave sums in index order.  Every thread
-// returns the same value; two calls may follow each other (the barrier at the top protects the previous call's reads).
-__device__ __forceinline__ float block_sum(float v, float* sm4) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sm4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((sm4[0] + sm4[1]) + sm4[2]) + sm4[3];
-}
+using var_ppo::block_sum;                                      // (ppo_row.h: the fixed-order workgroup sum)
 
 // ---- var_rollout_move -----------------------------------------------------------------------------------------------------
 // The piece copy, the segment table and its host-side planning live in rollout_move.h (var_rollout_move_at shares them).
 using var_move::MoveTable;
-using var_move::overlap;
+using var_move::overlap;                                       // (var_rollout_returns)
 
 __global__ void __launch_bounds__(kThreads) rollout_move_kernel(MoveTable tab, const int* __restrict__ ind, int n_env, int n_src_env) {
     const unsigned b = blockIdx.x;
@@ -102,8 +94,7 @@ __global__ void __launch_bounds__(kThreads) rollout_returns_kernel(const float* 
 // One thread per row, rows grid-strided over at most kPpoMaxWG workgroups.  A row writes its own gradients (1 / M is known);
 // the sums -- value loss, action loss, entropy, d total / d logstd -- go workgroup by workgroup into the context's partials
 // (agent-scope stores), and the LAST workgroup to take a ticket folds them (policy_dist_kernel's counter: no wait anywhere).
-constexpr int kMaxGauss = 4, kMaxCat = 16;
-constexpr float kHalfLog2Pi = 0.9189385332046727f;
+// The row math, the fold and the last step live in ppo_row.h (var_ppo_head_linear shares them).
 
 template <int KIND>
 __global__ void __launch_bounds__(kThreads) ppo_head_kernel(const float* __restrict__ head, const float* __restrict__ logstd,
@@ -118,86 +109,13 @@ __global__ void __launch_bounds__(kThreads) ppo_head_kernel(const float* __restr
     __shared__ int last_s;
     const int tid = threadIdx.x;
     const float invM = 1.f / (float)M;
-    float s_v = 0.f, s_a = 0.f, s_e = 0.f, s_ls[kMaxGauss] = {0.f, 0.f, 0.f, 0.f};
+    var_ppo::RowSums s;
     for (long row = (long)blockIdx.x * kThreads + tid; row < M; row += (long)gridDim.x * kThreads) {
-        // value loss (ppo.py:73-82)
-        const float v = value[row], rt = returns[row];
-        float gv;
-        if (clipped) {
-            const float vp = value_preds[row], dv = v - vp;
-            const float vpc = vp + fminf(fmaxf(dv, -clip), clip);
-            const float e1 = v - rt, e2 = vpc - rt, l1 = e1 * e1, l2 = e2 * e2;
-            s_v += fmaxf(l1, l2);
-            const float w1 = l1 > l2 ? 1.f : (l1 == l2 ? 0.5f : 0.f), w2 = 1.f - w1;
-            const float gate = (dv >= -clip && dv <= clip) ? 1.f : 0.f;
-            gv = w1 * (2.f * e1) + (w2 * gate) * (2.f * e2);
-        } else {
-            const float e1 = rt - v;
-            s_v += e1 * e1;
-            gv = -2.f * e1;
-        }
-        g_value[row] = (0.5f * vcoef * invM) * gv;
-        const float ol = old_logp[row], ad = adv[row];
-        if (KIND == 0) {
-            float lp = 0.f, diff[kMaxGauss], var[kMaxGauss];
-#pragma unroll
-            for (int d = 0; d < kMaxGauss; ++d) {
-                diff[d] = 0.f; var[d] = 1.f;
-                if (d < n) {
-                    const float ls = logstd[d], sd = expf(ls);
-                    diff[d] = ((const float*)action)[row * n + d] - head[row * n + d];
-                    var[d] = sd * sd;
-                    lp += -(diff[d] * diff[d]) / (2.f * var[d]) - ls - kHalfLog2Pi;
-                }
-            }
-            if (logp_out) logp_out[row] = lp;
-            const float ratio = expf(lp - ol);
-            const float s1 = ratio * ad, s2 = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip) * ad;
-            s_a += fminf(s1, s2);
-            const float glp = s1 <= s2 ? -(ad * ratio) * invM : 0.f;      // d action_loss / d logp
-#pragma unroll
-            for (int d = 0; d < kMaxGauss; ++d) {
-                if (d < n) {
-                    g_head[row * n + d] = glp * (diff[d] / var[d]);
-                    s_ls[d] += glp * ((diff[d] * diff[d]) / var[d] - 1.f);
-                }
-            }
-        } else {
-            float l[kMaxCat];
-            float mx = head[row * n];
-#pragma unroll
-            for (int k = 0; k < kMaxCat; ++k) { l[k] = k < n ? head[row * n + k] : 0.f; if (k > 0 && k < n) mx = fmaxf(mx, l[k]); }
-            float sum = 0.f;
-#pragma unroll
-            for (int k = 0; k < kMaxCat; ++k) sum += k < n ? expf(l[k] - mx) : 0.f;
-            const float lse = logf(sum);
-            const long long a = ((const long long*)action)[row];
-            float la = __builtin_nanf(""), H = 0.f, pk[kMaxCat];   // an action outside [0, n) gives NaN, never a wild read
-#pragma unroll
-            for (int k = 0; k < kMaxCat; ++k) {
-                l[k] = (l[k] - mx) - lse;                          // log p_k
-                pk[k] = k < n ? expf(l[k]) : 0.f;
-                H -= k < n ? pk[k] * l[k] : 0.f;
-                la = (long long)k == a && k < n ? l[k] : la;
-            }
-            if (logp_out) logp_out[row] = la;
-            const float ratio = expf(la - ol);
-            const float s1 = ratio * ad, s2 = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip) * ad;
-            s_a += fminf(s1, s2);
-            s_e += H;
-            const float glp = s1 <= s2 ? -(ad * ratio) * invM : 0.f;
-            const float ge = ecoef * invM;                         // total has -ecoef * mean(H): dH / dl_k = -p_k (log p_k + H)
-#pragma unroll
-            for (int k = 0; k < kMaxCat; ++k) {
-                if (k < n) g_head[row * n + k] = glp * (((long long)k == a ? 1.f : 0.f) - pk[k]) + ge * (pk[k] * (l[k] + H));
-            }
-        }
+        var_ppo::ppo_row<KIND>(head + row * n, g_head + row * n, row, logstd, value, action, old_logp, adv, returns, value_preds, n,
+                               invM, clip, vcoef, ecoef, clipped, g_value, logp_out, s);
     }
     float tot[kPpoSums];
-    tot[0] = block_sum(s_v, sm4); tot[1] = block_sum(s_a, sm4); tot[2] = block_sum(s_e, sm4);
-#pragma unroll
-    for (int d = 0; d < kMaxGauss; ++d) tot[3 + d] = KIND == 0 ? block_sum(s_ls[d], sm4) : 0.f;
-    tot[7] = 0.f;
+    var_ppo::ppo_block_sums<KIND>(s, sm4, tot);
     if (gridDim.x > 1) {
         if (tid < kPpoSums - 1) {
             float mine = tot[0];
@@ -212,30 +130,10 @@ __global__ void __launch_bounds__(kThreads) ppo_head_kernel(const float* __restr
         }
         __syncthreads();
         if (!last_s) return;
-#pragma unroll
-        for (int q = 0; q < kPpoSums - 1; ++q) {
-            const bool live = (KIND == 0 ? q != 2 : q < 3) && tid < (int)gridDim.x;
-            tot[q] = block_sum(live ? join_load(part + q * kPpoMaxWG + tid) : 0.f, sm4);
-        }
+        var_ppo::ppo_fold_sums<KIND>(part, kPpoMaxWG, 1, (int)gridDim.x, sm4, tot);
     }
     if (tid != 0) return;
-    const float vl = 0.5f * (tot[0] * invM), al = -(tot[1] * invM);
-    float ent;
-    if (KIND == 0) {
-        float e = 0.f;
-#pragma unroll
-        for (int d = 0; d < kMaxGauss; ++d) {
-            if (d < n) {
-                e += (0.5f + kHalfLog2Pi) + logstd[d];
-                g_logstd[d] = tot[3 + d] - ecoef / (float)n;
-            }
-        }
-        ent = e / (float)n;
-    } else {
-        ent = tot[2] * invM;
-    }
-    out[0] = vl; out[1] = al; out[2] = ent;
-    out[3] = (vl * vcoef + al) - ent * ecoef;
+    var_ppo::ppo_finish<KIND>(tot, logstd, n, invM, vcoef, ecoef, out, g_logstd);
 }
 
 }  // namespace
@@ -243,30 +141,11 @@ __global__ void __launch_bounds__(kThreads) ppo_head_kernel(const float* __restr
 extern "C" int var_rollout_move(var_ctx* c, void* stream, const var_move_seg* segs, int n_seg, const int* ind, int n_env,
                                 int n_src_env) {
     if (!c) return VAR_ERR_ARG;
-    if (!segs || n_seg < 1 || n_seg > VAR_MOVE_MAX_SEGS) {
-        VAR_SET_ERR(c, "var_rollout_move: %d segments (1..%d, table not NULL)", n_seg, VAR_MOVE_MAX_SEGS);
-        return VAR_ERR_ARG;
-    }
-    if (n_env < 1 || n_src_env < 1 || (!ind && n_env > n_src_env)) {
-        VAR_SET_ERR(c, "var_rollout_move: n_env %d, n_src_env %d (>= 1; without an index list n_env <= n_src_env)", n_env, n_src_env);
-        return VAR_ERR_ARG;
-    }
     MoveTable tab{};
-    tab.n = n_seg;
-    size_t sext[VAR_MOVE_MAX_SEGS], dext[VAR_MOVE_MAX_SEGS];
+    size_t dext[VAR_MOVE_MAX_SEGS];
     unsigned long long blocks = 0;
-    for (int i = 0; i < n_seg; ++i) {
-        const int rc = var_move::move_plan_seg(c, "var_rollout_move", i, segs[i], n_env, n_src_env, 0, tab.s[i], blocks, sext[i], dext[i]);
-        if (rc != VAR_OK) return rc;
-    }
-    for (int i = 0; i < n_seg; ++i) {
-        for (int j = 0; j < n_seg; ++j) {
-            if (overlap(segs[i].dst, dext[i], segs[j].src, sext[j]) || (i < j && overlap(segs[i].dst, dext[i], segs[j].dst, dext[j]))) {
-                VAR_SET_ERR(c, "var_rollout_move: the destination range of segment %d overlaps a range of segment %d", i, j);
-                return VAR_ERR_ARG;
-            }
-        }
-    }
+    const int rc = var_move::move_plan_gather(c, "var_rollout_move", segs, n_seg, ind != nullptr, n_env, n_src_env, tab, blocks, dext);
+    if (rc != VAR_OK) return rc;
     VAR_HIP_CHECK(c, hipSetDevice(c->device));
     hipLaunchKernelGGL(rollout_move_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, tab, ind, n_env, n_src_env);
     VAR_HIP_CHECK(c, hipGetLastError());
@@ -311,17 +190,10 @@ extern "C" int var_ppo_head(var_ctx* c, void* stream, int kind, const float* hea
                             const float* value_preds, int n, long M, float clip, float value_coef, float entropy_coef,
                             int use_clipped_value_loss, float* out, float* g_head, float* g_value, float* g_logstd, float* logp) {
     if (!c) return VAR_ERR_ARG;
-    if (kind != 0 && kind != 1) { VAR_SET_ERR(c, "var_ppo_head: kind %d (0 DiagGaussian, 1 Categorical)", kind); return VAR_ERR_ARG; }
-    if (M < 1) { VAR_SET_ERR(c, "var_ppo_head: M %ld < 1", M); return VAR_ERR_ARG; }
-    const int nmax = kind == 0 ? kMaxGauss : kMaxCat;
-    if (n < 1 || n > nmax) { VAR_SET_ERR(c, "var_ppo_head: n %d outside 1..%d", n, nmax); return VAR_ERR_ARG; }
-    if (!head || !value || !action || !old_logp || !adv || !returns || !out || !g_head || !g_value ||
-        (use_clipped_value_loss && !value_preds) || (kind == 0 && (!logstd || !g_logstd))) {
-        VAR_SET_ERR(c, "var_ppo_head: a NULL pointer (only value_preds without the clipped value loss, and logstd / g_logstd "
-                       "of a Categorical head, may be NULL)");
-        return VAR_ERR_ARG;
-    }
-    if (!(clip >= 0.f)) { VAR_SET_ERR(c, "var_ppo_head: clip %g < 0", (double)clip); return VAR_ERR_ARG; }
+    const int rc = var_ppo::ppo_check_args(c, "var_ppo_head", kind, n, M, clip, value, action, old_logp, adv, returns, value_preds,
+                                           use_clipped_value_loss, logstd, g_logstd, out, g_value);
+    if (rc != VAR_OK) return rc;
+    if (!head || !g_head) { VAR_SET_ERR(c, "var_ppo_head: head and g_head must not be NULL"); return VAR_ERR_ARG; }
     VAR_HIP_CHECK(c, hipSetDevice(c->device));
     long wg = (M + kThreads - 1) / kThreads;
     if (wg > kPpoMaxWG) wg = kPpoMaxWG;

@@ -1,5 +1,6 @@
-// The strided row copy shared by var_rollout_move (rollout.hip: destinations the host computed) and var_rollout_move_at
-// (env_step.hip: destinations a device word selects): the segment table that travels to the kernel by value, the host code that
+// The strided row copy shared by var_rollout_move (rollout.hip: destinations the host computed), var_rollout_move_at
+// (env_step.hip: destinations a device word selects) and var_rollout_move_cursor (ppo_step.hip: the index list a device word
+// selects): the segment table that travels to the kernel by value, the host code that
 // checks and plans one segment, and the device code that moves one 16-byte piece.
 #pragma once
 #include "var_common.h"
@@ -100,6 +101,36 @@ inline int move_plan_seg(var_ctx* c, const char* who, int i, const var_move_seg&
     g.blk0 = (unsigned)blocks;
     blocks += g.cpr > 1 ? (unsigned long long)g.rows * g.cpr : (unsigned long long)((g.rows + g.rpb - 1) / g.rpb);
     if (blocks > 0x7fffffffull) { VAR_SET_ERR(c, "%s: more than 2^31 - 1 workgroups", who); return VAR_ERR_ARG; }
+    return VAR_OK;
+}
+
+// The whole table of an indexed gather (var_rollout_move, var_rollout_move_cursor): every check of include/var_hip.h, the plan in
+// `tab`, the launch's workgroups in `blocks`, each destination's extent in dext.  has_ind: an index list is given.
+inline int move_plan_gather(var_ctx* c, const char* who, const var_move_seg* segs, int n_seg, bool has_ind, int n_env, int n_src_env,
+                            MoveTable& tab, unsigned long long& blocks, size_t* dext) {
+    if (!segs || n_seg < 1 || n_seg > VAR_MOVE_MAX_SEGS) {
+        VAR_SET_ERR(c, "%s: %d segments (1..%d, table not NULL)", who, n_seg, VAR_MOVE_MAX_SEGS);
+        return VAR_ERR_ARG;
+    }
+    if (n_env < 1 || n_src_env < 1 || (!has_ind && n_env > n_src_env)) {
+        VAR_SET_ERR(c, "%s: n_env %d, n_src_env %d (>= 1; without an index list n_env <= n_src_env)", who, n_env, n_src_env);
+        return VAR_ERR_ARG;
+    }
+    tab.n = n_seg;
+    size_t sext[VAR_MOVE_MAX_SEGS];
+    blocks = 0;
+    for (int i = 0; i < n_seg; ++i) {
+        const int rc = move_plan_seg(c, who, i, segs[i], n_env, n_src_env, 0, tab.s[i], blocks, sext[i], dext[i]);
+        if (rc != VAR_OK) return rc;
+    }
+    for (int i = 0; i < n_seg; ++i) {
+        for (int j = 0; j < n_seg; ++j) {
+            if (overlap(segs[i].dst, dext[i], segs[j].src, sext[j]) || (i < j && overlap(segs[i].dst, dext[i], segs[j].dst, dext[j]))) {
+                VAR_SET_ERR(c, "%s: the destination range of segment %d overlaps a range of segment %d", who, i, j);
+                return VAR_ERR_ARG;
+            }
+        }
+    }
     return VAR_OK;
 }
 

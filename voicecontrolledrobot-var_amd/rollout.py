@@ -10,7 +10,9 @@ models/ppo/algo/ppo.py:PPO, plus ppo_loss, the loss lines of ppo.py:66-87 as one
     agent = PPO(reference_policy, ...); agent.update(rollouts); rollouts.after_update()
 
 The networks' evaluation forward and backward stay in PyTorch autograd: PPO takes the reference's Policy (the state_dict
-of ArmNetPolicy / IthorNetPolicy loads into it unchanged) or any module with the same .base / .dist.  GPU only: there is no
+of ArmNetPolicy / IthorNetPolicy loads into it unchanged) or any module with the same .base / .dist.  ppo_head_linear
+(csrc/ppo_step.hip: var_ppo_head_linear) is ppo_loss with the distribution head's Linear in front of it, PPO(..., fused_head=True)
+uses it, and PPO.capture(rollouts) replays whole minibatch steps as graphs (update_step.py).  GPU only: there is no
 CPU fallback, CPU tensors raise VarHipError."""
 import torch
 import torch.nn as nn
@@ -251,6 +253,70 @@ def ppo_loss(head, logstd, value, action, old_logp, adv, returns, value_preds, *
                           float(value_loss_coef), float(entropy_coef), bool(use_clipped_value_loss))
 
 
+class _PPOHeadLinear(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, features, weight, bias, logstd, value, action, old_logp, adv, returns, value_preds, kind, clip, vcoef, ecoef,
+                clipped):
+        if not torch.is_tensor(features) or not features.is_cuda:
+            raise VarHipError("ppo_head_linear: inputs must be CUDA tensors (no CPU fallback)")
+        dev = features.device
+        if features.dim() != 2 or features.shape[1] != 128:
+            raise VarHipError(f"ppo_head_linear: features must be (M, 128), got {tuple(features.shape)}")
+        if kind not in (0, 1):
+            raise VarHipError("ppo_head_linear: kind is 0 (DiagGaussian) or 1 (Categorical)")
+        if not torch.is_tensor(weight) or weight.dim() != 2 or weight.shape[1] != 128:
+            raise VarHipError("ppo_head_linear: weight must be (n, 128), nn.Linear's layout")
+        M, n = features.shape[0], weight.shape[0]
+        want_action = torch.float32 if kind == 0 else torch.int64
+
+        def prep(t, numel, name, dtype=torch.float32):
+            if not torch.is_tensor(t) or t.device != dev or t.dtype != dtype or t.numel() != numel:
+                raise VarHipError(f"ppo_head_linear: {name} must be a {dtype} tensor of {numel} elements on {dev}")
+            return t.detach().contiguous()
+
+        f, w, b = prep(features, M * 128, "features"), prep(weight, n * 128, "weight"), prep(bias, n, "bias")
+        ls = prep(logstd, n, "logstd") if kind == 0 else None
+        v, ol, ad, rt = prep(value, M, "value"), prep(old_logp, M, "old_logp"), prep(adv, M, "adv"), prep(returns, M, "returns")
+        vp = prep(value_preds, M, "value_preds") if clipped else None
+        a = prep(action, M * n if kind == 0 else M, "action", want_action)
+        c = Context.get(dev.index)
+        ws_bytes = c.lib.var_ppo_head_linear_workspace_bytes(int(kind), int(n), int(M))
+        if ws_bytes < 0:
+            raise VarHipError(f"ppo_head_linear: kind {kind} takes n in 1..{4 if kind == 0 else 16} and M >= 1 (n {n}, M {M})")
+        e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)          # noqa: E731
+        out, head, g_f, g_w, g_b, g_value = e(4), e(M, n), e(M, 128), e(n, 128), e(n), e(M)
+        g_logstd = e(n) if kind == 0 else None
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        c.check(c.lib.var_ppo_head_linear(c.handle, current_stream_handle(), int(kind), ptr(f), ptr(w), ptr(b), ptr(ls), ptr(v), ptr(a),
+                                          ptr(ol), ptr(ad), ptr(rt), ptr(vp), int(n), int(M), float(clip), float(vcoef), float(ecoef),
+                                          int(bool(clipped)), ptr(head), ptr(out), ptr(g_f), ptr(g_w), ptr(g_b), ptr(g_value),
+                                          ptr(g_logstd), ptr(ws), int(ws_bytes), None, 0, None, 0),
+                "var_ppo_head_linear")
+        ctx.save_for_backward(g_f, g_w, g_b, g_value, g_logstd)
+        ctx.shapes = (features.shape, weight.shape, bias.shape, value.shape, None if logstd is None else logstd.shape)
+        total, vl, al, ent = out[3], out[0], out[1], out[2]
+        ctx.mark_non_differentiable(vl, al, ent)
+        return total, vl, al, ent
+
+    @staticmethod
+    def backward(ctx, g_total, *_):
+        g_f, g_w, g_b, g_value, g_logstd = ctx.saved_tensors
+        fs, ws, bs, vs, ls = ctx.shapes
+        gl = (g_logstd * g_total).view(ls) if g_logstd is not None and ctx.needs_input_grad[3] else None
+        return ((g_f * g_total).view(fs), (g_w * g_total).view(ws), (g_b * g_total).view(bs), gl,
+                (g_value * g_total).view(vs)) + (None,) * 10
+
+
+def ppo_head_linear(features, weight, bias, logstd, value, action, old_logp, adv, returns, value_preds, *, kind, clip_param,
+                    value_loss_coef, entropy_coef, use_clipped_value_loss=True):
+    """ppo_loss with the distribution head's Linear in front of it (var_ppo_head_linear): features (M,128) are the actor
+    features, weight (n,128) / bias (n) dist.fc_mean's (kind 0) or dist.linear's (kind 1) parameters; the rest as ppo_loss.
+    Returns (total, value_loss, action_loss, dist_entropy); total.backward() hands features, weight, bias, logstd and value the
+    gradients the call left, scaled by the incoming gradient.  The losses are var_ppo_head's on the same head, bit for bit."""
+    return _PPOHeadLinear.apply(features, weight, bias, logstd, value, action, old_logp, adv, returns, value_preds, int(kind),
+                                float(clip_param), float(value_loss_coef), float(entropy_coef), bool(use_clipped_value_loss))
+
+
 class PPO:
     """models/ppo/algo/ppo.py:6-104 over the device-resident RolloutStorage and ppo_loss.  actor_critic: the reference's
     Policy, or any module with is_recurrent, .base(obs, hxs, masks, infer=False) -> (value, actor_features, hxs, extra) and
@@ -260,10 +326,11 @@ class PPO:
     as update_linear_schedule expects them, state_dict in optim.Adam's layout.  PPO(var_amd.bind_forward_gru(actor_critic), ...) puts
     the recurrent sequence of that evaluation (NNBase._forward_gru) on var_amd.masked_gru: forward and backward in HIP, no
     host read inside the update (gru_seq.py).  PPO(var_amd.bind_trunk(actor_critic), ...) puts the whole trunk behind imgCNN there,
-    forward and backward (trunk.py), and trains an ArmNetPolicy / IthorNetPolicy in place."""
+    forward and backward (trunk.py), and trains an ArmNetPolicy / IthorNetPolicy in place.  fused_head=True: dist.fc_mean / dist.linear
+    and its backward run inside the loss's call (ppo_head_linear), not as torch ops in front of ppo_loss."""
 
     def __init__(self, actor_critic, clip_param, ppo_epoch, num_mini_batch, value_loss_coef, entropy_coef, lr=None, eps=None,
-                 max_grad_norm=None, use_clipped_value_loss=True, config=None, fused_optimizer=False):
+                 max_grad_norm=None, use_clipped_value_loss=True, config=None, fused_optimizer=False, fused_head=False):
         self.config = config
         self.actor_critic = actor_critic
         self.clip_param = clip_param
@@ -283,6 +350,7 @@ class PPO:
         else:
             raise NotImplementedError("PPO: actor_critic.dist must be the reference's DiagGaussian or Categorical")
         self.fused_optimizer = bool(fused_optimizer)
+        self.fused_head = bool(fused_head)
         if self.fused_optimizer:
             self.optimizer = ClipAdam(actor_critic.parameters(), lr=lr, eps=eps, max_norm=max_grad_norm,
                                       policy=actor_critic if hasattr(actor_critic, "_arena_intact") else None)
@@ -299,12 +367,29 @@ class PPO:
         """(total, value_loss, action_loss, dist_entropy) of one minibatch of recurrent_generator."""
         obs, hxs, actions, value_preds, returns, masks, old_logp, adv = sample
         values, feats, _, _ = self.actor_critic.base(obs, hxs, masks, infer=False)
+        if self.fused_head:
+            dist = self.actor_critic.dist
+            lin, logstd = (dist.fc_mean, dist.logstd._bias) if self._kind == 0 else (dist.linear, None)
+            return ppo_head_linear(feats, lin.weight, lin.bias, logstd, values, actions, old_logp, adv, returns, value_preds,
+                                   kind=self._kind, clip_param=self.clip_param, value_loss_coef=self.value_loss_coef,
+                                   entropy_coef=self.entropy_coef, use_clipped_value_loss=self.use_clipped_value_loss)
         head, logstd = self._head(feats)
         return ppo_loss(head, logstd, values, actions, old_logp, adv, returns, value_preds, kind=self._kind,
                         clip_param=self.clip_param, value_loss_coef=self.value_loss_coef, entropy_coef=self.entropy_coef,
                         use_clipped_value_loss=self.use_clipped_value_loss)
 
+    def capture(self, rollouts, precision=None):
+        """The minibatch step of update(rollouts) as replayed graphs (update_step.py: UpdateStep), which update() then uses for
+        this storage.  Needs a policy bound with bind_convs, fused_optimizer=True, fused_head=True and the device-resident
+        RolloutStorage; precision defaults to bind_convs'.  Anything else raises VarHipError before a launch."""
+        from .update_step import UpdateStep
+        self._captured = UpdateStep(self, rollouts, precision)
+        return self._captured
+
     def update(self, rollouts):
+        captured = getattr(self, "_captured", None)
+        if captured is not None and rollouts is captured.storage:
+            return captured.update(rollouts)
         advantages = rollouts.advantages()
         stats = []
         for _ in range(self.ppo_epoch):
