@@ -897,6 +897,15 @@ int var_mfcc_psf(var_ctx* ctx, void* stream, const int16_t* pcm, const int* lens
  * MOTOR, S0, S1, SOUND, O0, OCC, GH, IM0, X, F0, FUSION, GI, IMR, ALL0, ALL1, C0, C1, A0, AFT; known once a chain launch has
  * run on the plan): the raw area of 8 rows x width (value, tag) pairs, value in the low word, the launch's epoch in the
  * high word; "chain": the whole pair area; "sync": the chain's 64 sync words ([3] = the epoch of the next launch).
+ * The reward plan's buffers (var_ithor_reward_plan / _pack / _step), after "irew_"; lengths are those of the PLAN's batch
+ * maxB, VAR_ERR_PLAN before a plan, VAR_ERR_ARG for an unknown name.  A step of B rows fills the first B rows of a1 (B, 32,
+ * 96, 96), p1..p4 (the fused conv + pool outputs: (B, 32, 48, 48), (B, 64, 24, 24), (B, 64, 12, 12), (B, 128, 6, 6)), a6
+ * (B, 1152), hid (B, 128); a goal step also s1 (clip, 64, 300, 20), s2 (clip, 64, 150, 13), s3 in the sequence layout
+ * (clip, 73, 448), gi (dir, clip*73 + t, 1536) with the direction stride B*73*1536, gh (the four split-K slabs of
+ * h W_hh^T above 16 clips: (slab, dir, clip, 1536) with B-based strides), hb (the two state slots, maxB*1024 floats
+ * apart, each (clip, [forward 512 | reverse 512]): slot 1 holds the last state h_73, slot 0 the one before), hs1 (clip,
+ * 128), hs2 (clip, 64), graw (clip, 3: the sound head before F.normalize); frozen: the parameter snapshot of the last
+ * var_ithor_reward_pack (var_ithor_param_count() floats).
  * var_debug_ithor_dense: one dense product of the iTHOR model's bf16 mode through the kernel its schedule would pick,
  * C[m + n*M] (+= when `add`) = sum_k A(m,k) B(k,n), A(m,k) = a[m*K + k] if a_kfast else a[k*M + m], B likewise with
  * b[n*K + k] | b[k*N + n]; nsplit > 1 writes split-K slabs C + s*M*N instead (device pointers, fp32).  Returns 1 when

@@ -769,8 +769,8 @@ int var_profile_read(var_ctx* c, float* total_ms, int* count) {
  * ("act1".."act5", "gact1".."gact5", "sact1".."sact4", "gsact1".."gsact4", "emb", "gemb", "wpack", the heads' rows
  * "emb_raw", "head_part", "graw", "ghid";
  * iTHOR workspace: "ithor_s1".."ithor_s3", "ithor_gs1".."ithor_gs3": sound conv outputs / their gradients, sized for
- * the planned batch; the acting forwards' workspaces: "arm_..." (armnet.hip), "ipol_..." (ithor_policy.hip), names in
- * include/var_hip.h). */
+ * the planned batch; the acting forwards' workspaces: "arm_..." (armnet.hip), "ipol_..." (ithor_policy.hip), the reward plan's: "irew_..."
+ * (ithor_reward.hip), names in include/var_hip.h). */
 int var_debug_buffer(var_ctx* c, const char* name, void** ptr, long* nfloats) {
     CHECK_CTX(c);
     if (!name || !ptr || !nfloats) return VAR_ERR_ARG;
@@ -780,6 +780,7 @@ int var_debug_buffer(var_ctx* c, const char* name, void** ptr, long* nfloats) {
     if (!strncmp(name, "ithor_", 6)) return ithor_debug_buffer(c, name + 6, ptr, nfloats);
     if (!strncmp(name, "arm_", 4)) return armnet_debug_buffer(c, name + 4, ptr, nfloats);
     if (!strncmp(name, "ipol_", 5)) return ithor_policy_debug_buffer(c, name + 5, ptr, nfloats);
+    if (!strncmp(name, "irew_", 5)) return ithor_reward_debug_buffer(c, name + 5, ptr, nfloats);
     if (!c->ws) { VAR_SET_ERR(c, "var_debug_buffer: no plan"); return VAR_ERR_PLAN; }
     for (int l = 1; l <= 5; l++) {
         char a[16], g[16];

@@ -327,6 +327,27 @@ void ithor_reward_free(var_ctx* c) {
     c->irew = nullptr;
 }
 
+// var_debug_buffer's "irew_" names, lengths those of the PLAN's batch (a step of B rows fills the first B rows of each, except
+// gi (dir stride B * 73 * 1536) and gh (slab stride 2 * B * 1536, dir stride B * 1536), which follow B; the two hb slots are
+// maxB * 1024 apart): a1, p1..p4, a6 (maxB, 1152), hid (maxB, 128), s1, s2, s3 (clip, 73, 448), gi, gh, hb, hs1, hs2, graw,
+// frozen (the parameter snapshot)
+int ithor_reward_debug_buffer(var_ctx* c, const char* name, void** ptr, long* nfloats) {
+    rew_state* st = rew(c);
+    if (!st) { VAR_SET_ERR(c, "var_debug_buffer: no var_ithor_reward_plan"); return VAR_ERR_PLAN; }
+    const long B = st->maxB;
+    const struct { const char* name; float* p; long n; } tab[] = {
+        {"a1", st->a1, B * 32 * 96 * 96}, {"p1", st->p[1], B * 32 * 48 * 48}, {"p2", st->p[2], B * 64 * 24 * 24},
+        {"p3", st->p[3], B * 64 * 12 * 12}, {"p4", st->p[4], B * 128 * 6 * 6}, {"a6", st->a6, B * kIRaw}, {"hid", st->hid, B * kHidI},
+        {"s1", st->s[1], B * 64 * 300 * 20}, {"s2", st->s[2], B * 64 * 150 * 13}, {"s3", st->s[3], B * kSeq * kGin},
+        {"gi", st->GI, 2 * B * kSeq * kG3}, {"gh", st->GH, (long)kRecSplit * 2 * B * kG3}, {"hb", st->Hb, 2 * B * kSRaw},
+        {"hs1", st->hs1, B * 128}, {"hs2", st->hs2, B * 64}, {"graw", st->graw, B * 3}, {"frozen", st->frozen, st->L.total},
+    };
+    for (const auto& e : tab)
+        if (!strcmp(name, e.name)) { *ptr = e.p; *nfloats = e.n; return VAR_OK; }
+    VAR_SET_ERR(c, "var_debug_buffer: unknown iTHOR reward buffer '%s'", name);
+    return VAR_ERR_ARG;
+}
+
 extern "C" {
 
 int var_ithor_reward_plan(var_ctx* c, int max_batch, int img_hw) {

@@ -415,6 +415,7 @@ int snd3_bf16_wgrad(var_ctx* c, hipStream_t s, float* dw, float* slab, int nclip
 int ithor_debug_buffer(var_ctx* c, const char* name, void** ptr, long* nfloats);
 int armnet_debug_buffer(var_ctx* c, const char* name, void** ptr, long* nfloats);           // armnet.hip: var_debug_buffer's "arm_" names
 int ithor_policy_debug_buffer(var_ctx* c, const char* name, void** ptr, long* nfloats);     // ithor_policy.hip: its "ipol_" names
+int ithor_reward_debug_buffer(var_ctx* c, const char* name, void** ptr, long* nfloats);     // ithor_reward.hip: its "irew_" names
 
 // gru_bf16.hip: one launch per GRU time step and pass (recurrent product on bf16 MFMA + gate arithmetic), bf16 mode
 long gru_bf16_workspace_bytes(int maxclips);
