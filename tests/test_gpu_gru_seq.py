@@ -20,6 +20,19 @@ from tests import gru_seq_cpu as gc
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 1, 4, 64), (3, 2, 128, 512), (3, 2, 128, 1024), (5, 16, 128, 512), (4, 17, 20, 64), (7, 5, 128, 512)]
+# (T, N, I, H) that first run a path of csrc/gru_seq.hip's tiling.  A wave's share of a step's product is H/64 k-steps of 16 forward
+# and 3H/64 backward, taken 8, then 4, then 1 at a time (mac_all); the shapes above give 1 | 8 | 16 and 3 | 24 | 48.
+TILING_SHAPES = [
+    (2, 3, 8, 256),        # forward 4 alone, backward 8 + 4
+    (2, 3, 8, 320),        # forward 4 + 1, backward 8 + 4 + 1 + 1 + 1
+    (2, 33, 129, 128),     # three env blocks, the last with one env; a second M tile of one row in d_x and d_w_ih; 1 + 1 | 4 + 1 + 1
+    (1, 64, 1024, 64),     # both upper limits at once, and T = 1
+    (2, 48, 1, 192),       # I = 1 (a reduction of one k); backward 8 + 1
+    (3, 17, 128, 1024),    # a ragged second env block at the iTHOR hidden size
+    (2, 16, 20, 64),       # 32 rows: the last size on the batched products' 32-column tile
+    (3, 11, 20, 64),       # 33 rows: the first on the 64-column tile
+]
+SHAPES += TILING_SHAPES    # every shape's bounds: 20 draws (gru_seq_cpu.gru_distance)
 KEYS = ("x", "hxs", "masks", "w_ih", "w_hh", "b_ih", "b_hh")
 SENT = -77.0
 
@@ -79,6 +92,9 @@ def reference(shape, golden_dir):
 def check(got, ref, bounds, keys, what):
     worst = {k: gc.rel(got[k], ref[k]) for k in keys}
     print(what, {k: (f"{worst[k]:.3g}", f"bound {bounds[k]:.3g}") for k in keys})
+    ratio = {k: worst[k] / bounds[k] if bounds[k] else (0.0 if worst[k] == 0 else np.inf) for k in keys}
+    top = max(keys, key=ratio.get)
+    print(f"{what}: worst error / bound {ratio[top]:.3f} at {top}")
     for k in keys:
         assert np.isfinite(got[k]).all(), k
         assert worst[k] <= bounds[k], (what, k, worst[k], bounds[k])
@@ -157,7 +173,7 @@ def test_one_call_equals_chained_single_steps(var_amd, shape):
 
 
 # ---- 6: determinism -----------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape", [(5, 16, 128, 512), (4, 17, 20, 64), (3, 2, 128, 1024)])
+@pytest.mark.parametrize("shape", [(5, 16, 128, 512), (4, 17, 20, 64), (3, 2, 128, 1024)] + TILING_SHAPES[:2])
 def test_two_runs_give_equal_bits(var_amd, shape):
     d = gc.gru_inputs(*shape, seed=13)
     a, b = run(var_amd, d, True), run(var_amd, d, True)

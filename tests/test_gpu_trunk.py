@@ -3,7 +3,8 @@ the float64 checker of tests/trunk_cpu.py and the fixtures made from the referen
 
 Bounds are measured, not chosen (trunk_cpu.trunk_distance): per output, saved activation and gradient array four times the distance
 of torch's own fp32 CPU evaluation from float64, the largest over 20 seeded draws at the tested shape, relative to the array's
-largest magnitude; five such distances against the fixtures.  The float64 backward is taken at the GPU's own ReLU gates, and the
+largest magnitude (10 draws at 224 to 258 rows and 5 from 481, where a draw costs a second of host time); five such distances against
+the fixtures.  The float64 backward is taken at the GPU's own ReLU gates, and the
 units whose gate differs from the float64 forward's are counted and must lie within rounding of zero (trunk_cpu's docstring).
 Every test prints what it measured.  Determinism, the GRU part, graph replay and the extent of the writes are bit for bit."""
 import ctypes
@@ -17,7 +18,10 @@ from tests import trunk_cpu as tc
 
 pytestmark = pytest.mark.gpu
 
-CASES = [(k, T, N) for k in (0, 1) for T, N in ((1, 1), (3, 2), (2, 17), (7, 5))] + [(0, 33, 4), (1, 1, 5)]
+SMALL_CASES = [(k, T, N) for k in (0, 1) for T, N in ((1, 1), (3, 2), (2, 17), (7, 5))] + [(0, 33, 4), (1, 1, 5)]      # 20 draws each
+# the row counts on either side of a change of tiling in csrc/trunk.hip (trunk_cpu.THRESHOLD_SHAPES says which): 10 draws each up
+# to 258 rows, 5 from 481
+CASES = SMALL_CASES + [(k, T, N) for T, N in tc.THRESHOLD_SHAPES for k in (0, 1)]
 VARIANTS = tuple(tc.VARIANTS)
 SENT = -77.0
 
@@ -90,15 +94,21 @@ def compare(kind, got, ref_fwd, ref, dist, margin, keys=None):
 # ---- 1: forward, every saved activation and backward against float64 --------------------------------------------------------------
 @pytest.mark.parametrize("kind,T,N", CASES)
 def test_forward_saved_and_backward_match_float64(var_amd, kind, T, N):
+    """Up to 132 rows, then (T, N) = (14, 16), (15, 15), (6, 43), (13, 37), (9, 57), (16, 62), (20, 50): 224, 225, 258, 481, 513, 992 and
+    1000 rows, each the smallest with N <= 64 on one side of a switch -- the 32-row tile of product_tile<2> with a ragged last tile
+    (from 225 rows for the J >= 1024 data gradients, 481 for J = 512, 897 for d_occ, 993 for J = 256), a second and a third pass of
+    column_sums (from 257 and 513 rows), three and four environment blocks in the recurrent sequence (N = 37, 57).  The layers
+    with J <= 128 change tile at 2017, 4065 and 8161 rows; those sizes are NOT run: a float64 reference of the recurrent sequence
+    there takes far longer than a test may, and product_tile<2> is one piece of code for every layer."""
     seed = tc.find_seed(kind, T, N, 100 * (kind + 1) + T + N)
     P, d = tc.trunk_inputs(kind, T, N, seed)
     got = run(var_amd, kind, P, d, VARIANTS)
     gates = tc.gates_of(got["all"], kind)
     ref_fwd = tc.evaluate(kind, P, d, torch.float64)["all"]
     ref = tc.evaluate(kind, P, d, torch.float64, gates=gates, variants=VARIANTS)
-    dist = tc.trunk_distance(kind, T, N)
+    dist = tc.case_distance(kind, T, N)
     flips, ratio = tc.flipped_gates(kind, gates, ref_fwd, dist["all"])
-    print(f"kind {kind} T {T} N {N} seed {seed}: {flips} flipped gates, worst |pre-activation| / allowance {ratio:.3f}")
+    print(f"kind {kind} T {T} N {N} rows {T * N} seed {seed} draws {tc.draws(T, N)}: {flips} flipped gates, worst |pre-activation| / allowance {ratio:.3f}")
     assert flips <= tc.MAX_FLIPS and ratio <= 1.0, (flips, ratio)
     for v in VARIANTS:
         assert np.array_equal(bits(got[v]["h_T"]), bits(got[v]["act.gru"][-N:]))      # h_T IS the last step's rows
@@ -136,6 +146,25 @@ def test_two_runs_give_equal_bits_and_the_gru_part_is_masked_gru(var_amd, kind):
     out, h_T = var_amd.masked_gru(dev(a["all"]["act.imgMotorMlp.2"]), dev(d["hxs"]), dev(d["masks"]), gru.weight_ih_l0, gru.weight_hh_l0,
                                   gru.bias_ih_l0, gru.bias_hh_l0)
     assert np.array_equal(bits(host(out)), bits(a["all"]["act.gru"])) and np.array_equal(bits(host(h_T)), bits(a["all"]["h_T"]))
+
+
+@pytest.mark.parametrize("kind", [0, 1])
+def test_a_longer_sequence_leaves_earlier_steps_untouched(var_amd, kind):
+    """A step's output does not depend on later steps: steps 0 .. 13 (210 rows) of the T = 15, N = 15 call equal the T = 14 call on
+    the same inputs cut to 14 steps, bit for bit, in both outputs and every saved activation.  (Both sizes run the forward on
+    16-row tiles; the tile width is the float64 cases' business.)"""
+    T, N, Tc = 15, 15, 14
+    rows = Tc * N
+    P, d = tc.trunk_inputs(kind, T, N, tc.find_seed(kind, T, N, 100 * (kind + 1) + T + N))
+    cut = {k: (v if k in ("hxs", "d_hT") else v[:rows]) for k, v in d.items()}
+    base = tc.module_from_params(kind, P).cuda()
+    whole, part = run(var_amd, kind, P, d, base=base)["all"], run(var_amd, kind, P, cut, base=base)["all"]
+    keys = [k for k in part if k in ("value", "actor_features") or k.startswith("act.")]
+    assert len(keys) == 2 + len(tc.layers(kind)) + 1
+    for k in keys:
+        assert part[k].shape[0] == rows and whole[k].shape[0] == T * N, k
+        assert np.array_equal(bits(whole[k][:rows]), bits(part[k])), k
+    assert not np.array_equal(whole["h_T"], part["h_T"])            # (the fifteenth step did run)
 
 
 @pytest.mark.parametrize("kind", [0, 1])

@@ -1,6 +1,7 @@
 """Host-side checks of the PPO update's recurrent sequence (no GPU): the float64 checker of tests/gru_seq_cpu.py reproduces the
 fixture made from the reference's NNBase._forward_gru (tests/golden/gru_seq_t7.npz), its two restatements agree, the public
-names exist and refuse what they cannot run before any library call."""
+names exist and refuse what they cannot run before any library call; and the faults a third env block and a second M tile can
+have, injected into torch's fp32 evaluation standing in for the device, are rejected by the bounds of the shape that first has them."""
 import types
 
 import numpy as np
@@ -143,3 +144,39 @@ def test_forward_gru_and_binding_refuse_what_they_cannot_run():
     assert var_amd.bind_forward_gru(pol) is pol and var_amd.bind_forward_gru(pol.base) is pol.base
     with pytest.raises(E):
         pol.base(x, hxs, masks)                                    # bound: the CPU call now fails loudly
+
+
+# ---- the shapes that first run a tiling path: that their bounds would notice what the path can get wrong -------------------------
+def _stand_in(shape):
+    """torch's fp32 CPU evaluation of the segmented form standing in for the device at a GPU case's own inputs."""
+    d = gc.gru_inputs(*shape, seed=100 + sum(shape))
+    return gc.evaluate(d, torch.float32, "segmented"), gc.evaluate(d, torch.float64, "steps"), gc.gru_bounds(*shape, True)
+
+
+def test_a_third_env_block_fault_is_rejected_at_33_envs():
+    """One env of the third block of 16 (env 32 of 33) given its neighbour's state at every step; no case before had a third block."""
+    shape = T, N, I, H = (2, 33, 129, 128)
+    assert -(-N // 16) == 3 and -(-17 // 16) == 2                   # (17 envs was the most run before)
+    t32, ref, bound = _stand_in(shape)
+    out = t32["out"].reshape(T, N, H).copy()
+    out[:, 32] = out[:, 31]
+    bad = {"out": out.reshape(T * N, H), "h_T": out[-1]}
+    for k in gc.OUTPUTS:
+        ok, b = gc.rel(t32[k], ref[k]) / bound[k], gc.rel(bad[k], ref[k]) / bound[k]
+        print(f"env 32 with env 31's state, {k} at {shape}: sound {ok:.3f} of the bound, the fault {b:.3g} x")
+        assert ok <= 1.0 < b, (k, ok, b)
+
+
+@pytest.mark.parametrize("stale", [0.0, -77.0])
+def test_an_unwritten_second_m_tile_is_rejected_at_129_inputs(stale):
+    """d_x (rows, I) and d_w_ih (3H, I) are products with M = I on tiles of 128: at I = 129 input 128 is a second tile of one row;
+    left unwritten it holds whatever the buffer held.  With I <= 128, all that ran before, there is no second tile."""
+    shape = T, N, I, H = (2, 33, 129, 128)
+    assert -(-I // 128) == 2 and -(-128 // 128) == 1
+    t32, ref, bound = _stand_in(shape)
+    for k in ("d_x", "d_w_ih"):
+        bad = t32[k].copy()
+        bad[:, 128:] = stale
+        ok, b = gc.rel(t32[k], ref[k]) / bound[k], gc.rel(bad, ref[k]) / bound[k]
+        print(f"input 128 of {k} left at {stale} at {shape}: sound {ok:.3f} of the bound, the fault {b:.3g} x")
+        assert ok <= 1.0 < b, (k, ok, b)

@@ -13,7 +13,8 @@ first one from its base seed at which torch's fp32 CPU forward and the float64 f
 Bounds (tests/rollout_cpu.py's rule): per output, saved activation and gradient array, four times the distance of torch's own fp32
 CPU evaluation from float64 -- the largest over 20 such draws at the tested shape, relative to the array's largest magnitude
 (trunk_distance); five times against the fixture made from the reference.  The yardstick is torch against float64, never the
-kernel."""
+kernel.  The shapes at which the kernels change their tiling (THRESHOLD_SHAPES, 224 to 1000 rows) take 10 draws up to 300 rows
+and 5 above: host time."""
 import functools
 import os
 
@@ -229,6 +230,90 @@ def trunk_distance(kind, T, N, seeds=20, variants=tuple(VARIANTS)):
     return worst
 
 
+# ---- the row counts at which csrc/trunk.hip changes its tiling -------------------------------------------------------------------
+# (T, N) of the small cases: 20 draws each
+SMALL_SHAPES = {0: ((1, 1), (3, 2), (2, 17), (7, 5), (33, 4)), 1: ((1, 1), (3, 2), (2, 17), (7, 5), (1, 5))}
+# (T, N) -> what first runs there; 10 draws up to 300 rows and 5 above (a draw costs 0.6 s | 1.1 s of an 8-core host's time at 225
+# rows and 1.1 s | 2.2 s at 1000 for kind 0 | 1, about a third of that on 16 cores, where the 225-row iTHOR case still took 9 s
+# with 20 draws.  The largest over fewer draws is the smaller number, so the bound is the tighter one)
+THRESHOLD_SHAPES = {
+    (14, 16): "224 rows: the last size with 16-row tiles everywhere but the two full-tile weight gradients",
+    (15, 15): "225 rows: d_feat and kind 1's GRU-output gradient on 32-row tiles, the last tile holds 1 row",
+    (6, 43): "258 rows: a second column_sums pass of 2 rows",
+    (13, 37): "481 rows: the J = 512 data gradients and the out = 512 forwards on 32-row tiles, last tile 1 row; three env blocks",
+    (9, 57): "513 rows: a third column_sums pass of 1 row; four env blocks, the last with 9 envs",
+    (16, 62): "992 rows: the last size before the J = 256 switch",
+    (20, 50): "1000 rows: the J = 256 data gradients and out = 256 forwards on 32-row tiles; d_occ (from 897)",
+}
+LARGEST_SMALL = (33, 4)
+
+
+def draws(T, N):
+    """How many draws trunk_distance takes at a shape of the GPU tests."""
+    rows = T * N
+    return 20 if rows <= 132 else (10 if rows <= 300 else 5)
+
+
+def case_distance(kind, T, N):
+    """trunk_distance with the draw count of the shape (one cache entry per shape for every test that asks)."""
+    return trunk_distance(kind, T, N, draws(T, N)) if (T, N) in THRESHOLD_SHAPES else trunk_distance(kind, T, N)
+
+
+def tile_rows(I, J):
+    """Rows (and columns) of the output tile product_job picks for an I x J product: 32 where that still gives 256 workgroups."""
+    return 32 if -(-I // 32) * -(-J // 32) >= 256 else 16
+
+
+def column_passes(rows):
+    """[(first row, rows)] of column_sums' passes through LDS."""
+    return [(b, min(256, rows - b)) for b in range(0, rows, 256)]
+
+
+def pre_activation_gradients(kind, P, d, dtype):
+    """layer -> G (M, out), the gradient of the 'all' objective with respect to the layer's pre-activation, on the CPU in `dtype`
+    (numpy, `dtype` kept): what the backward's dX, dW and db jobs of that layer read as their gated operand."""
+    tt = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dtype)   # noqa: E731
+    Pt = {k: tt(P[k]).requires_grad_() for k in param_names(kind)}
+    t = {k: tt(d[k]) for k in input_names(kind)}
+    value, feats, h_T, _acts, pre = trunk_forward(kind, Pt, t)
+    obj = (value * tt(d["d_value"])).sum() + (feats * tt(d["d_actor_features"])).sum() + (h_T * tt(d["d_hT"])).sum()
+    names = [name for name, *_ in layers(kind)]
+    return {n: g.numpy() for n, g in zip(names, torch.autograd.grad(obj, [pre[n] for n in names]))}
+
+
+def faulty_column_sums(G, fault=None):
+    """emul_column_sums (the kernel's own order) with one fault: 'first_pass_only' stops after rows 0 .. 255; 'last_pass_twice' adds
+    a short last pass that is not the first a second time (a stale LDS buffer read again).  With one pass neither changes
+    anything."""
+    acc = np.zeros(G.shape[1], np.float64)
+    passes = column_passes(G.shape[0])
+    for i, (base, n) in enumerate(passes):
+        part = _pass_sum(G, base, n)
+        acc = acc + part
+        if fault == "last_pass_twice" and i and i == len(passes) - 1 and n < 256:
+            acc = acc + part
+        if fault == "first_pass_only":
+            break
+    return acc.astype(np.float32)
+
+
+def faulty_tile_rows(a, fault, tile=32):
+    """A copy of the (I, J) result `a` of a product on `tile`-row tiles with one fault in its rows: 'last_row_zero' (the ragged
+    tile's guard drops a live row), 'last_row_repeats' (the clamp min(.., I - 1) taken one short: row I - 1 holds row I - 2's
+    value), 'halves_exchanged' (the two 16-row halves of the first tile stored to each other's rows)."""
+    a = np.array(a, copy=True)
+    if fault == "last_row_zero":
+        a[-1] = 0.0
+    elif fault == "last_row_repeats":
+        a[-1] = a[-2]
+    elif fault == "halves_exchanged":
+        assert tile == 32 and a.shape[0] >= 32
+        a[:16], a[16:32] = a[16:32].copy(), a[:16].copy()
+    else:
+        raise ValueError(fault)
+    return a
+
+
 def trunk_bounds(kind, T, N, variant="all", margin=MARGIN):
     return {k: margin * v for k, v in trunk_distance(kind, T, N)[variant].items()}
 
@@ -348,11 +433,26 @@ def emul_product(Pm, Qm):
     return (parts[0] + parts[1]) + (parts[2] + parts[3])
 
 
-def emul_column_sums(G):
-    acc = np.zeros(G.shape[1], np.float32)
-    for row in G:
+def _pass_sum(G, base, n):
+    """One pass of column_sums in float64: rows base + rl + 16 i added in order of i, then the sixteen partial sums in order of
+    rl (rows past the end count as zero)."""
+    blk = np.zeros((256, G.shape[1]), np.float64)
+    blk[:n] = G[base:base + n]
+    part = np.zeros((16, G.shape[1]), np.float64)
+    for row in blk.reshape(16, 16, -1):                           # [i][rl]
+        part = part + row
+    acc = np.zeros(G.shape[1], np.float64)
+    for row in part:
         acc = acc + row
     return acc
+
+
+def emul_column_sums(G):
+    """column_sums' order: 256 rows a pass, carried in float64, the passes in order, one rounding to fp32 at the end."""
+    acc = np.zeros(G.shape[1], np.float64)
+    for base, n in column_passes(G.shape[0]):
+        acc = acc + _pass_sum(G, base, n)
+    return acc.astype(np.float32)
 
 
 def _sum_in_order(arrays):
@@ -364,7 +464,7 @@ def _sum_in_order(arrays):
 
 def emulate(kind, P, d, variants=("all",)):
     """evaluate()'s result (without 'pre.*') from an fp32 numpy emulation of the kernels' order of additions: operand sums
-    (a0 + a1) + a2 on load, emul_product for every forward product, dX and dW, the bias added after the fold, db in row order; the
+    (a0 + a1) + a2 on load, emul_product for every forward product, dX and dW, the bias added after the fold, db carried in float64; the
     recurrent sequence itself is torch's fp32 masked_gru_steps and its autograd."""
     f = np.float32
     acts = {k: d[k].astype(f) for k in ("feat", "motor_in", "sound_in", "occ") if k in d}

@@ -30,7 +30,7 @@ struct Op {
     int vec;             // ks == 1 and every row 16-byte aligned: four k in one load
 };
 // kind 0: c[i * ldc + j] = act(bias[j] + sum_k p(i, k) q(j, k)), I x J outputs, tj tiles of 16 rt along j
-// kind 1: c[j] = sum_{m < I} p(m, j) in row order, J columns (p.rs = the row stride, p.ks = 1)
+// kind 1: c[j] = sum_{m < I} p(m, j) carried in float64, J columns (p.rs = the row stride, p.ks = 1)
 struct Job {
     Op p, q;
     float* c;
@@ -137,12 +137,16 @@ __device__ __forceinline__ void product_tile(const Job& jb, int tile, float* __r
     }
 }
 
-// 16 columns per workgroup: 256 rows at a time go through LDS (sixteen loads per thread in flight), then thread c < 16 adds its
-// column's in row order
-__device__ __forceinline__ void column_sums(const Job& jb, int tile, float* __restrict__ red) {
+// 16 columns per workgroup, 256 rows a pass (sixteen loads per thread in flight; rows past the end count as zero).  The sum is
+// carried in float64 and rounded to fp32 once, at the end: thread (c, rl) adds rows base + rl + 16 i in order of i, thread c < 16
+// adds the sixteen partial sums of its column in order of rl through LDS, and the passes are added in order.  A bias gradient is
+// a sum that may cancel (critic_linear's is ONE number, the sum of d_value): an fp32 chain in row order missed the tests' bound,
+// four times torch's fp32 distance from float64, from 481 rows up, and an fp32 tree still did at 1000 (DESIGN.md has the figures).
+__device__ __forceinline__ void column_sums(const Job& jb, int tile, float* __restrict__ red_f) {
+    double* red = (double*)red_f;                              // 256 doubles of the buffer
     const int tid = threadIdx.x, c = tid & 15, rl = tid >> 4;
     const int j0 = tile * 16, col = min(j0 + c, jb.J - 1), rows = jb.I;
-    float v = 0.f;
+    double v = 0.0;
     for (int base = 0; base < rows; base += 256) {
         float t[16];
 #pragma unroll
@@ -150,22 +154,23 @@ __device__ __forceinline__ void column_sums(const Job& jb, int tile, float* __re
             const int m = base + rl + 16 * i;
             t[i] = m < rows ? op_at(jb.p, (long)m * jb.p.rs + col) : 0.f;
         }
+        double s = 0.0;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) red[(rl + 16 * i) * 16 + c] = t[i];
+        for (int i = 0; i < 16; ++i) s += (double)t[i];
+        red[rl * 16 + c] = s;
         __syncthreads();
         if (tid < 16) {
-            const int n = min(256, rows - base);
-#pragma unroll 8
-            for (int m = 0; m < n; ++m) v += red[m * 16 + tid];
+#pragma unroll 1                                              // (unrolled, the sixteen doubles cost the kernel half its occupancy)
+            for (int m = 0; m < 16; ++m) v += red[m * 16 + tid];
         }
         __syncthreads();
     }
-    if (tid < 16 && j0 + tid < jb.J) jb.c[j0 + tid] = v;
+    if (tid < 16 && j0 + tid < jb.J) jb.c[j0 + tid] = (float)v;
 }
 
 template <bool BWD>
 __global__ void __launch_bounds__(256) trunk_stage_kernel(const Jobs jobs) {
-    __shared__ float red[4 * 16 * 64];
+    __shared__ __attribute__((aligned(16))) float red[4 * 16 * 64];
     int j = 0;
     while (j + 1 < jobs.n && (int)blockIdx.x >= jobs.first[j + 1]) ++j;
     const Job& jb = jobs.j[j];
