@@ -119,10 +119,11 @@ def layer_inputs(kind, image, acts, images=None):
     return xs
 
 
-def layer_refs(kind, P, d, got, images=None, what=("act", "g", "w", "b"), layers=None):
+def layer_refs(kind, P, d, got, images=None, what=("act", "g", "w", "b"), layers=None, rounding=True):
     """Float64 references of the arrays in `got` ('act.<l>', 'g.<l>' as fp32 numpy arrays from the GPU): 'act.<l>' from the GPU's
     map below, 'g.<l>' (l below the last) from the GPU's g of the layer above and the GPU's map of layer l, 'g.<last>' from d_feat,
-    'd.<l>.weight' / '.bias' from the GPU's g_l and x_l.  images: restrict the per-image arrays ('act', 'g') to these images."""
+    'd.<l>.weight' / '.bias' from the GPU's g_l and x_l.  images: restrict the per-image arrays ('act', 'g') to these images.
+    rounding=False: the same products on unrounded operands (the fp32 mode's references)."""
     geo = geometry(kind)
     names = [n for n, *_ in geo]
     layers = names if layers is None else layers
@@ -136,21 +137,22 @@ def layer_refs(kind, P, d, got, images=None, what=("act", "g", "w", "b"), layers
             continue
         w, b = tt(P[name + ".weight"]), tt(P[name + ".bias"])
         if "act" in what:
-            ref["act." + name] = conv_forward(xs[l], w, b, stride, pad, f64)
+            ref["act." + name] = conv_forward(xs[l], w, b, stride, pad, f64, rounding)
         if "g" in what:
             if l == len(geo) - 1:
                 a = pick(tt(got["act." + name], torch.float32))
                 ref["g." + name] = pick(tt(d["d_feat"], f64)).reshape(a.shape) * (a > 0).to(f64)
             else:
                 up, _ci, _co, s2, p2, _pl = geo[l + 1]
-                dx = data_grad(pick(tt(got["g." + up], torch.float32)), tt(P[up + ".weight"]), xs[l + 1].shape, s2, p2, f64)
+                dx = data_grad(pick(tt(got["g." + up], torch.float32)), tt(P[up + ".weight"]), xs[l + 1].shape, s2, p2, f64,
+                               rounding)
                 ref["g." + name] = gate_below(dx, pick(tt(got["act." + name], torch.float32)), geo[l][5])
         if "w" in what or "b" in what:
             if xs_all is None:
                 xs_all = layer_inputs(kind, d["image"], got)
             g = tt(got["g." + name], torch.float32)
             if "w" in what:
-                ref["d." + name + ".weight"] = weight_grad(xs_all[l], g, w.shape, stride, pad, f64)
+                ref["d." + name + ".weight"] = weight_grad(xs_all[l], g, w.shape, stride, pad, f64, rounding)
             if "b" in what:
                 ref["d." + name + ".bias"] = bias_grad(g, f64)
     return {k: v.numpy() for k, v in ref.items()}
@@ -178,9 +180,9 @@ def draws_for(B):
     return 20 if B <= 5 else 3
 
 
-def product_distances(kind, ops):
-    """{array: rel(torch fp32 CPU evaluation, float64 evaluation)} of every layer's rounded-operand products over the operands
-    `ops` (a chain() result: x_l from its maps, g_l its gradients)."""
+def product_distances(kind, ops, rounding=True):
+    """{array: rel(torch fp32 CPU evaluation, float64 evaluation)} of every layer's rounded-operand products (rounding=False: the
+    same products on unrounded operands) over the operands `ops` (a chain() result: x_l from its maps, g_l its gradients)."""
     geo = geometry(kind)
     f32, f64 = torch.float32, torch.float64
     image = ops["image"]
@@ -188,40 +190,42 @@ def product_distances(kind, ops):
     out = {}
     for l, (name, _cin, _cout, stride, pad, _pooled) in enumerate(geo):
         w, b, g = ops["P"][name + ".weight"], ops["P"][name + ".bias"], ops["g." + name].float()
-        out["act." + name] = rel(conv_forward(xs[l], w, b, stride, pad, f32).numpy(), conv_forward(xs[l], w, b, stride, pad, f64).numpy())
-        out["d." + name + ".weight"] = rel(weight_grad(xs[l], g, w.shape, stride, pad, f32).numpy(),
-                                           weight_grad(xs[l], g, w.shape, stride, pad, f64).numpy())
+        out["act." + name] = rel(conv_forward(xs[l], w, b, stride, pad, f32, rounding).numpy(),
+                                  conv_forward(xs[l], w, b, stride, pad, f64, rounding).numpy())
+        out["d." + name + ".weight"] = rel(weight_grad(xs[l], g, w.shape, stride, pad, f32, rounding).numpy(),
+                                           weight_grad(xs[l], g, w.shape, stride, pad, f64, rounding).numpy())
         out["d." + name + ".bias"] = rel(bias_grad(g, f32).numpy(), bias_grad(g, f64).numpy())
         if l:
             below = ops["act." + geo[l - 1][0]].float()
-            a32 = gate_below(data_grad(g, w, xs[l].shape, stride, pad, f32), below, geo[l - 1][5])
-            a64 = gate_below(data_grad(g, w, xs[l].shape, stride, pad, f64), below, geo[l - 1][5])
+            a32 = gate_below(data_grad(g, w, xs[l].shape, stride, pad, f32, rounding), below, geo[l - 1][5])
+            a64 = gate_below(data_grad(g, w, xs[l].shape, stride, pad, f64, rounding), below, geo[l - 1][5])
             out["g." + geo[l - 1][0]] = rel(a32.numpy(), a64.numpy())
     out["g." + geo[-1][0]] = 0.0                                      # the last layer's gate is a selection of d_feat: exact
     return out
 
 
-def draw_operands(kind, B, seed):
+def draw_operands(kind, B, seed, rounding=True):
     P, d = cc.convstack_params(kind, seed), cc.convstack_data(kind, B, seed)
-    ops = chain(kind, P, d, torch.float32)
+    ops = chain(kind, P, d, torch.float32, rounding)
     ops["P"] = {k: tt(v) for k, v in P.items()}
     ops["image"] = d["image"]
     return ops
 
 
-def bounds(kind, B, draws=None):
-    """{array: MARGIN * the largest product_distances over the draws at this shape}; memoised per (kind, B)."""
+def bounds(kind, B, draws=None, rounding=True):
+    """{array: MARGIN * the largest product_distances over the draws at this shape}; memoised per (kind, B, rounding)."""
     draws = draws_for(B) if draws is None else draws
-    if (kind, B) not in _BOUNDS or _BOUNDS[(kind, B)][0] < draws:
+    key = (kind, B, rounding)
+    if key not in _BOUNDS or _BOUNDS[key][0] < draws:
         worst = {}
         for i in range(draws):
-            for k, v in product_distances(kind, draw_operands(kind, B, CASE_SEED + i)).items():
+            for k, v in product_distances(kind, draw_operands(kind, B, CASE_SEED + i, rounding), rounding).items():
                 worst[k] = max(worst.get(k, 0.0), v)
-        _BOUNDS[(kind, B)] = (draws, {k: MARGIN * v for k, v in worst.items()})
-    return _BOUNDS[(kind, B)][1]
+        _BOUNDS[key] = (draws, {k: MARGIN * v for k, v in worst.items()})
+    return _BOUNDS[key][1]
 
 
-def weight_grad_bound(kind, B, name, draws=3):
+def weight_grad_bound(kind, B, name, draws=3, rounding=True):
     """MARGIN * the largest distance of one layer's weight gradient over `draws` draws at batch B (the grid-wrap sizes: the whole
     chain in float64 would take minutes there).  A draw's x_l is the fp32 chain's forward up to that layer; its g_l is a seeded
     Gaussian map gated by the layer's own ReLU pattern: the fp32-against-float64 distance of a sum depends on the number and spread
@@ -234,13 +238,13 @@ def weight_grad_bound(kind, B, name, draws=3):
         P, d = cc.convstack_params(kind, CASE_SEED + i), cc.convstack_data(kind, B, CASE_SEED + i)
         x = tt(cc.as_float_image(d["image"]))
         for nm, _ci, _co, s2, p2, pooled in geo[:l]:
-            a = conv_forward(x, tt(P[nm + ".weight"]), tt(P[nm + ".bias"]), s2, p2, torch.float32)
+            a = conv_forward(x, tt(P[nm + ".weight"]), tt(P[nm + ".bias"]), s2, p2, torch.float32, rounding)
             x = pool(a) if pooled else a
         w = tt(P[name + ".weight"])
-        a = conv_forward(x, w, tt(P[name + ".bias"]), stride, pad, torch.float32)
+        a = conv_forward(x, w, tt(P[name + ".bias"]), stride, pad, torch.float32, rounding)
         g = torch.randn(a.shape, generator=torch.Generator().manual_seed(CASE_SEED + i)) * (a > 0).float()
-        worst = max(worst, rel(weight_grad(x, g, w.shape, stride, pad, torch.float32).numpy(),
-                               weight_grad(x, g, w.shape, stride, pad, torch.float64).numpy()))
+        worst = max(worst, rel(weight_grad(x, g, w.shape, stride, pad, torch.float32, rounding).numpy(),
+                               weight_grad(x, g, w.shape, stride, pad, torch.float64, rounding).numpy()))
     return MARGIN * worst
 
 

@@ -12,8 +12,9 @@ bit for bit.
 Batch sizes: 1, 2, 3, 5, 15, and both sides of every size at which a product's 128-row tile count first exceeds one -- 9 B pixels
 of the image stacks' last maps (14 | 15), 25 B of kind 0's 5 x 5 map (5 | 6), 36 B of the parity classes of kind 0's stride-2 data
 gradient (3 | 4) -- at which the weight gradient of a 25 B- or 9 B-pixel layer is first split in two (8 | 9, 24 | 25), and, for
-kind 2, at which its weight gradients take another slab of eight images (8 | 9, 16 | 17, 24 | 25).  The form of a fold and the
-number of bias partials depend on the layer alone."""
+kind 2, at which its weight gradients take another slab of eight images (8 | 9, 16 | 17, 24 | 25); kind 2 also at the update's 200
+images, at the limit of 1024 (128 slabs) and one below it (a ragged 128th slab).  The form of a fold and the number of bias
+partials depend on the layer alone.  The image stacks' larger batches are tests/test_gpu_convstack_large.py's."""
 import ctypes
 
 import numpy as np
@@ -25,7 +26,7 @@ from tests import trunk_cpu as tc
 
 pytestmark = pytest.mark.gpu
 
-BATCHES = {0: (1, 2, 3, 4, 5, 6, 8, 9, 14, 15, 24, 25), 1: (1, 2, 3, 5, 14, 15, 24, 25), 2: (1, 2, 3, 5, 6, 8, 9, 14, 15, 16, 17, 24, 25)}
+BATCHES = {0: (1, 2, 3, 4, 5, 6, 8, 9, 14, 15, 24, 25), 1: (1, 2, 3, 5, 14, 15, 24, 25), 2: (1, 2, 3, 5, 6, 8, 9, 14, 15, 16, 17, 24, 25, 200, 1023, 1024)}
 # uint8 images at every size, float images at three of them
 CASES = [(k, B, True) for k in (0, 1, 2) for B in BATCHES[k]] + [(k, B, False) for k in (0, 1, 2) for B in (2, 5, 15)]
 SENT = -77.0
