@@ -105,6 +105,16 @@ int var_arm_encoder_fwd(var_ctx* ctx, void* stream, const float* params,
  * Envs/vec_env/vec_pretext_normalize.py:96-101 (`calcReward`: torch.sum(a * b, dim=1)) as ONE launch on `stream`; the sum
  * runs over k in index order in fp32. */
 int var_row_dot(var_ctx* ctx, void* stream, const float* a, const float* b, int rows, int dim, float* out);
+/* calcReward's embedding reward with config.RLRewardSoundSound on (vec_pretext_normalize.py:96-101), ONE launch on `stream`:
+ *     a = sum_k image_feat[r][k] * goal_feat[r][k];  b = sum_k cur_feat[r][k] * goal_feat[r][k]      (var_row_dot's sums, fp32)
+ *     out[r] = a + b (one fp32 add);  out_img[r] = a, out_snd[r] = b where those are not NULL
+ * -- the reference's grouping: two float32 np.sum(axis=1), one float32 add; the float64 add of envReward is
+ * var_reward_norm_step's, which takes `out` as its dot.  cur_feat = NULL drops the second term: out has var_row_dot's bits and
+ * out_snd, where given, is 0.  rows x dim f32, dim <= 64.  VAR_ERR_ARG, nothing launched: image_feat / goal_feat / out NULL,
+ * rows < 1, dim outside 1..64. */
+int var_reward_dots(var_ctx* ctx, void* stream, const float* image_feat, const float* goal_feat,
+                    const float* cur_feat /* NULL: no second term */, int rows, int dim, float* out,
+                    float* out_img /* may be NULL */, float* out_snd /* may be NULL */);
 /* Arms the NEXT var_arm_encoder_fwd with an image: it also leaves reward_out[b] = <image_feat[b], goal_feat[b]> (3 floats per
  * row, var_row_dot's sum) -- the intrinsic reward of VAR/pretext_base.py's calcReward.  Where the image head is a launch of its
  * own that finishes the embeddings (save_for_bwd = 2, 84 x 84, at most 16 rows: the RL stage's envs) the dot rides in that launch
@@ -550,12 +560,14 @@ int var_ppo_head(var_ctx* ctx, void* stream, int kind /*0 DiagGaussian, 1 Catego
  * entry waits for another workgroup, allocates or synchronises; there is no time-out and no status word.
  *
  * var_reward_norm_step: one workgroup, float64, each operation rounded once in the reference's grouping.  Inputs, device:
- * dot (N) f32 or NULL (= 0): <image_feat, goal_sound_feat>; env_reward (N) f64; done (N) u8; bad (N) u8 or NULL (no
+ * dot (N) f32 or NULL (= 0): embReward -- <image_feat, goal_sound_feat>, or with config.RLRewardSoundSound on the fp32 sum
+ * <image_feat, goal_sound_feat> + <current_sound_feat, goal_sound_feat> that var_reward_dots / var_ithor_reward_step_ex leave
+ * (the second term is part of `dot`: this entry is the same in both modes); env_reward (N) f64; done (N) u8; bad (N) u8 or NULL (no
  * 'bad_transition').  normalise = 0 is the wrapper built with ret=False.  State, device float64: ret (N), rms[3] = {mean, var,
  * count} of running_mean_std.py:4-35 (a fresh one is {0, 1, 1e-4}), episode (3N) = the running sum of the un-normalised step
  * reward, the sum of the last finished episode, the number of finished episodes per env (RL.py:171-176: the host reads it when it
  * logs), slot int32[2].  Outputs: reward, masks, bad_masks (N,1) f32, orig_reward (N) f64 (origStepReward, :53).  Per env i:
- *     rews = (double)dot[i] + env_reward[i]                                      (calcReward, :96-101; RLRewardSoundSound off)
+ *     rews = (double)dot[i] + env_reward[i]                                     (calcReward, :96-101: embReward + envReward)
  *     ret[i] = ret[i] * gamma + rews                                                                                      (:55)
  *     normalise: bm = mean_i ret, bv = mean_i (ret - bm) * (ret - bm); delta = bm - mean; total = count + N;
  *         m2 = (var * count + bv * N) + (((delta * delta) * count) * N) / total;
@@ -836,8 +848,37 @@ int var_convstack_bwd_ex(var_ctx* ctx, void* stream, int kind, const float* cons
  * pool, the stride-2 conv 6, one tail: both Linear layers, F.normalize and the dot); with a goal 7 + 3 convolutions + the
  * input projection + 73 GRU steps (one launch each up to 16 clips: recurrent product of both directions, b_hh, gates and h'
  * fused; two launches each beyond, 72 products) + the 3 Linear layers of the sound head.  No kernel waits for another
- * workgroup: there is no time-out and no status word. */
+ * workgroup: there is no time-out and no status word.
+ *
+ * config.RLRewardSoundSound (vec_pretext_normalize.py:82-101: the wrapper also embeds O['current_sound'] on EVERY step and
+ * rewards <image_feat, goal_feat> + <current_sound_feat, goal_feat>):
+ *   var_ithor_reward_plan_ex  var_ithor_reward_plan with flags; var_ithor_reward_plan is flags 0 and reserves what it always
+ *       did.  VAR_IREW_SOUND_SOUND (bit 0) plans for max(max_batch, min(2 * max_batch, 16)) rows -- room for the goal and the
+ *       current clips of up to 8 envs in ONE pass of the sound branch -- and reserves craw, the current clips' head output.
+ *       Other bits: VAR_ERR_ARG.  A plan made with the bit serves every call; one made without it is replaced (never shrunk)
+ *       when the bit is asked for, and the weights must be packed again.
+ *   var_ithor_reward_step_ex  cur_mfcc = NULL: var_ithor_reward_step -- same launches, same bits, cur_feat / reward_img /
+ *       reward_snd untouched.  With cur_mfcc (B,1,600,40), VAR_ERR_PLAN unless the plan has bit 0 and VAR_ERR_ARG without
+ *       cur_feat: cur_feat (B,3) = the current clips' embedding, reward_img = sum_d image_feat * goal_feat, reward_snd =
+ *       sum_d cur_feat * goal_feat (each where not NULL), reward = reward_img + reward_snd in one fp32 add: var_reward_dots'
+ *       grouping.  The clips run through the goal clips' kernels, which treat clips independently, on the route
+ *       var_ithor_reward_step takes for B clips -- a clip's embedding has the bits it has as a goal clip at the same B:
+ *         goal and current clips, 2B <= 16: ONE pass of 2B clips (conv 1 once per clip set, then one launch per layer and one
+ *             per GRU time step for both: 8 envs fill the fused step's 16 columns); goal rows 0..B-1, current rows B..2B-1
+ *             of every sound buffer, the current clips' head output in graw rows B..2B-1;
+ *         otherwise: one pass of B clips per clip set over the same buffers (the current clips last: the buffers hold theirs
+ *             afterwards), the current clips' head output in craw.
+ *       The tail stays one launch: its last workgroup also normalises the current clips' embedding and forms both dots.
+ *       Launches: 7 + one sound pass (80 up to 16 clips) for a current-only step; 7 + 81 for a merged goal step; 7 + two
+ *       passes otherwise. */
+#define VAR_IREW_SOUND_SOUND 1
 int var_ithor_reward_plan(var_ctx* ctx, int max_batch, int img_hw);
+int var_ithor_reward_plan_ex(var_ctx* ctx, int max_batch, int img_hw, int flags);
+int var_ithor_reward_step_ex(var_ctx* ctx, void* stream, const float* params,
+                             const void* image, int image_is_u8, long image_bstride,
+                             const float* goal_mfcc /* | NULL */, const float* cur_mfcc /* | NULL */, int B,
+                             float* image_feat, float* goal_feat, float* cur_feat, float* reward,
+                             float* reward_img /* | NULL */, float* reward_snd /* | NULL */);
 int var_ithor_reward_pack(var_ctx* ctx, void* stream, const float* params);
 int var_ithor_reward_step(var_ctx* ctx, void* stream, const float* params,
                           const void* image, int image_is_u8, long image_bstride,
@@ -904,8 +945,10 @@ int var_mfcc_psf(var_ctx* ctx, void* stream, const int16_t* pcm, const int* lens
  * (clip, 73, 448), gi (dir, clip*73 + t, 1536) with the direction stride B*73*1536, gh (the four split-K slabs of
  * h W_hh^T above 16 clips: (slab, dir, clip, 1536) with B-based strides), hb (the two state slots, maxB*1024 floats
  * apart, each (clip, [forward 512 | reverse 512]): slot 1 holds the last state h_73, slot 0 the one before), hs1 (clip,
- * 128), hs2 (clip, 64), graw (clip, 3: the sound head before F.normalize); frozen: the parameter snapshot of the last
- * var_ithor_reward_pack (var_ithor_param_count() floats).
+ * 128), hs2 (clip, 64), graw (clip, 3: the sound head before F.normalize), craw (clip, 3: the same of the current clips of a
+ * sound-sound step that ran them in a pass of their own; a merged pass leaves them in graw rows B..2B-1; zero floats long
+ * without VAR_IREW_SOUND_SOUND); frozen: the parameter snapshot of the last var_ithor_reward_pack (var_ithor_param_count()
+ * floats).
  * var_debug_ithor_dense: one dense product of the iTHOR model's bf16 mode through the kernel its schedule would pick,
  * C[m + n*M] (+= when `add`) = sum_k A(m,k) B(k,n), A(m,k) = a[m*K + k] if a_kfast else a[k*M + m], B likewise with
  * b[n*K + k] | b[k*N + n]; nsplit > 1 writes split-K slabs C + s*M*N instead (device pointers, fp32).  Returns 1 when

@@ -13,8 +13,11 @@ RL.py:137-141, 171-185) -- as ONE replayed HIP graph over buffers the act step a
         collect.observe(image, extras, env_reward, done)             # replay 2: nothing is read back
 
 DeviceReturnNormalizer is the normaliser alone (reward.ReturnNormalizer with its state on the device).  GPU only: there is no
-CPU fallback.  Not here: the act replay inside the same graph (the value and action of slot T would be stale after the
-update), RLRewardSoundSound and _obfilt (off in both reference configurations)."""
+CPU fallback.  config.RLRewardSoundSound is IntrinsicReward(encoder, sound_sound=True): every observe() then takes the step's
+current sound as well, the same replay embeds it (var_ithor_reward_step_ex, or var_arm_encoder_fwd's negative clip +
+var_reward_dots) and the normaliser's dot is <image_feat, goal_feat> + <current_sound_feat, goal_feat>.  Not here: the act
+replay inside the same graph (the value and action of slot T would be stale after the update) and _obfilt (off in both
+reference configurations)."""
 import numpy as np
 import torch
 
@@ -145,8 +148,9 @@ def insert_segments(act, rollouts, reward, bad_masks):
 
 class CollectStep:
     """One env step of the collection loop (RL.py:163-185 without the simulator) as one replay: the reward step of the frozen
-    encoder (var_arm_encoder_fwd + var_row_dot / var_set_reward_dot, or var_ithor_reward_step), var_reward_norm_step and one
-    var_rollout_move_at, captured twice -- with and without a new goal sound.  The act step's own buffers are the operands:
+    encoder (var_arm_encoder_fwd + var_row_dot / var_set_reward_dot, or var_ithor_reward_step; with reward.sound_sound
+    var_arm_encoder_fwd + var_reward_dots, or var_ithor_reward_step_ex), var_reward_norm_step and one var_rollout_move_at,
+    captured twice -- with and without a new goal sound.  The act step's own buffers are the operands:
     act_step.obs['image'] is the encoder's input, obs['image_feat'] / obs['goal_sound_feat'] its outputs (the cached goal
     embedding of the later steps lives there), act_step.masks the normaliser's mask output; nothing is copied between the parts.
 
@@ -155,10 +159,13 @@ class CollectStep:
     RolloutStorage whose image dtype is the act step's.  gamma, cliprew, epsilon, normalize: VecPretextNormalize's (normalize =
     its `ret`).  Refuses with VarHipError what it cannot run.
 
-    reset(image, extras, goal_sound): envs.reset() + RL.py:137-141.  observe(image, extras, env_reward, done, bad=None,
-    goal_sound=None): one env step.  extras: {'robot_pose': (N,2)} (Kuka) / {'occupancy': (N,1,9,9)} (iTHOR).  Host arrays go
-    through pinned staging buffers with non-blocking copies (an event guards the block's reuse); device tensors are copied, or
-    used in place when they ARE the buffers (act_step.obs[...], self.env_reward, self.done, self.bad, self.goal_sound).
+    reset(image, extras, goal_sound): envs.reset() + RL.py:137-141 (the reference discards the reset's reward, so it takes no
+    current sound).  observe(image, extras, env_reward, done, bad=None, goal_sound=None, current_sound=None): one env step;
+    with reward.sound_sound current_sound is required on every step -- self.dot then carries the sum of the two terms,
+    self.dot_img / self.dot_snd the terms and self.cur_feat (N,3) the current sound's embedding -- and ignored otherwise.
+    extras: {'robot_pose': (N,2)} (Kuka) / {'occupancy': (N,1,9,9)} (iTHOR).  Host arrays go through pinned staging buffers with non-blocking copies (an event guards the block's reuse); device tensors are copied, or
+    used in place when they ARE the buffers (act_step.obs[...], self.env_reward, self.done, self.bad, self.goal_sound,
+    self.current_sound).
     norm: the DeviceReturnNormalizer (reward, bad_masks, orig_reward, episode, state()); episode_stats() reads the episode block."""
 
     def __init__(self, reward, act_step, rollouts, gamma=0.99, cliprew=10., epsilon=1e-8, normalize=True):
@@ -168,8 +175,6 @@ class CollectStep:
         from .rollout import RolloutStorage
         if not isinstance(reward, IntrinsicReward) or not isinstance(act_step, ActStep) or not isinstance(rollouts, RolloutStorage):
             raise VarHipError("CollectStep(reward: IntrinsicReward, act_step: ActStep, rollouts: RolloutStorage)")
-        if getattr(reward, "sound_sound", False):
-            raise VarHipError("CollectStep: RLRewardSoundSound is not provided (False in both reference configurations)")
         m = reward.model
         flat = m.flat_parameters()
         if not flat.is_cuda:
@@ -195,6 +200,11 @@ class CollectStep:
         self._extra = [k for k in obs if k not in ('image', 'image_feat', 'goal_sound_feat')]
         self.goal_sound = torch.zeros((N,) + tuple(m.config.sound_dim), dtype=torch.float32, device=dev)
         self.dot = torch.zeros(N, device=dev)
+        ss = self.sound_sound = bool(getattr(reward, "sound_sound", False))
+        if ss:                                                   # RLRewardSoundSound: O['current_sound'] of every step, and what it adds
+            self.current_sound = torch.zeros_like(self.goal_sound)
+            self.cur_feat = torch.zeros(N, 3, device=dev)
+            self.dot_img, self.dot_snd = torch.zeros(N, device=dev), torch.zeros(N, device=dev)
         # env_reward f64 | done u8 | bad u8: one device block, one staging copy
         self._small = torch.zeros(8 * N + 2 * N, dtype=torch.uint8, device=dev)
         self.env_reward = self._small[:8 * N].view(torch.float64)
@@ -206,10 +216,16 @@ class CollectStep:
         if ithor:
             if flat.numel() != c.lib.var_ithor_param_count():
                 raise VarHipError("parameter arena does not match var_ithor_param_count()")
-            c.check(c.lib.var_ithor_reward_plan(c.handle, N, hw), "var_ithor_reward_plan")
+            c.check(c.lib.var_ithor_reward_plan_ex(c.handle, N, hw, int(ss)), "var_ithor_reward_plan_ex")
             c.check(c.lib.var_ithor_reward_pack(c.handle, current_stream_handle(), ptr(flat)), "var_ithor_reward_pack")
 
-            def encoder(with_goal):
+            def encoder(with_goal, with_cur=ss):
+                if with_cur:
+                    c.check(c.lib.var_ithor_reward_step_ex(c.handle, current_stream_handle(), ptr(flat), ptr(image), is_u8,
+                                                           image.stride(0), ptr(self.goal_sound) if with_goal else None,
+                                                           ptr(self.current_sound), N, ptr(img_feat), ptr(goal_feat), ptr(self.cur_feat),
+                                                           ptr(self.dot), ptr(self.dot_img), ptr(self.dot_snd)), "var_ithor_reward_step_ex")
+                    return
                 c.check(c.lib.var_ithor_reward_step(c.handle, current_stream_handle(), ptr(flat), ptr(image), is_u8, image.stride(0),
                                                     ptr(self.goal_sound) if with_goal else None, N, ptr(img_feat), ptr(goal_feat),
                                                     ptr(self.dot)), "var_ithor_reward_step")
@@ -217,8 +233,16 @@ class CollectStep:
             c.ensure_plan(N, hw)
             w = m.hip_weights(c, force=True)                     # the frozen model's own packed image; the graphs keep its address
 
-            def encoder(with_goal):
+            def encoder(with_goal, with_cur=ss):
                 w.bind()
+                if with_cur:                                     # the current sound is the forward's negative clip; no dot is armed
+                    c.check(c.lib.var_arm_encoder_fwd(c.handle, current_stream_handle(), ptr(flat), ptr(image), is_u8, image.stride(0),
+                                                      ptr(self.goal_sound) if with_goal else None, ptr(self.current_sound), N, hw,
+                                                      ptr(img_feat), ptr(goal_feat) if with_goal else None, ptr(self.cur_feat), None, None,
+                                                      2), "var_arm_encoder_fwd")
+                    c.check(c.lib.var_reward_dots(c.handle, current_stream_handle(), ptr(img_feat), ptr(goal_feat), ptr(self.cur_feat), N,
+                                                  3, ptr(self.dot), ptr(self.dot_img), ptr(self.dot_snd)), "var_reward_dots")
+                    return
                 if not with_goal:                                # the forward itself leaves <image_feat, goal_feat>
                     c.check(c.lib.var_set_reward_dot(c.handle, ptr(goal_feat), ptr(self.dot)), "var_set_reward_dot")
                 c.check(c.lib.var_arm_encoder_fwd(c.handle, current_stream_handle(), ptr(flat), ptr(image), is_u8, image.stride(0),
@@ -235,7 +259,7 @@ class CollectStep:
             c.check(c.lib.var_rollout_move_at(c.handle, current_stream_handle(), self._segs, len(self._segs),
                                               self.norm.slot.data_ptr() + 4, N), "var_rollout_move_at")
 
-        bodies = {True: lambda: body(True), False: lambda: body(False), "reset": lambda: encoder(True)}
+        bodies = {True: lambda: body(True), False: lambda: body(False), "reset": lambda: encoder(True, False)}
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream())
         self._graphs = {}
@@ -255,9 +279,10 @@ class CollectStep:
         torch.cuda.current_stream().wait_stream(side)
         self._slot = rollouts.step                               # host mirror of slot[0]
         self._have_goal = False
-        # pinned staging: image | extras | goal sound | env_reward, done, bad -- each 16-byte aligned
+        # pinned staging: image | extras | goal sound | current sound (sound-sound) | env_reward, done, bad -- each 16-byte aligned
         self._stage, off = {}, 0
-        for name, t in [('image', image)] + [(k, obs[k]) for k in self._extra] + [('goal_sound', self.goal_sound), ('small', self._small)]:
+        sounds = [('goal_sound', self.goal_sound)] + ([('current_sound', self.current_sound)] if ss else [])
+        for name, t in [('image', image)] + [(k, obs[k]) for k in self._extra] + sounds + [('small', self._small)]:
             self._stage[name] = (off, t)
             off += (t.numel() * t.element_size() + 15) // 16 * 16
         self._pin = torch.empty(off, dtype=torch.uint8).pin_memory()
@@ -303,7 +328,7 @@ class CollectStep:
             raise VarHipError(f"CollectStep: the storage is at step {self.rollouts.step}, the device slot at {self._slot}: "
                               "RolloutStorage.insert was called in between (reset() takes the storage's step over)")
 
-    def _plans(self, image, extras, goal_sound, small):
+    def _plans(self, image, extras, goal_sound, small, current_sound=None):
         obs = self.act_step.obs
         if not isinstance(extras, dict) or sorted(extras) != sorted(self._extra):
             raise VarHipError(f"CollectStep: extras must be a dict of {self._extra}")
@@ -311,6 +336,8 @@ class CollectStep:
         plans += [(k, self._plan_input(k, extras[k], obs[k]), obs[k]) for k in self._extra]
         if goal_sound is not None:
             plans.append(('goal_sound', self._plan_input('goal_sound', goal_sound, self.goal_sound), self.goal_sound))
+        if current_sound is not None:
+            plans.append(('current_sound', self._plan_input('current_sound', current_sound, self.current_sound), self.current_sound))
         return plans + [(name, self._plan_input(name, v, buf), buf) for name, v, buf in small]
 
     def _stage_inputs(self, plans, small_names=()):
@@ -362,18 +389,25 @@ class CollectStep:
         self._have_goal = True
 
     @torch.no_grad()
-    def observe(self, image, extras, env_reward, done, bad=None, goal_sound=None):
+    def observe(self, image, extras, env_reward, done, bad=None, goal_sound=None, current_sound=None):
         """One env step: obs, reward, done, infos of envs.step -> the storage (RL.py:164-185).  env_reward (N) float64, done /
-        bad (N) uint8 or bool (bad: 'bad_transition' in info; None = none).  Returns the (N,1) float32 reward buffer; nothing is
-        read back from the device.  The next act is act_step(act_step.obs, act_step.masks)."""
+        bad (N) uint8 or bool (bad: 'bad_transition' in info; None = none).  current_sound: O['current_sound'], required when the
+        reward has sound_sound (a step without it raises and changes nothing: storage, normaliser and device slot stay) and
+        ignored otherwise.  Returns the (N,1) float32 reward buffer; nothing is read back from the device.  The next act is
+        act_step(act_step.obs, act_step.masks)."""
         self._check_ready()
+        if self.sound_sound and current_sound is None:
+            raise VarHipError("CollectStep.observe: the reward has sound_sound on -- every step needs current_sound "
+                              "(vec_pretext_normalize.py:82-95)")
+        if not self.sound_sound:
+            current_sound = None
         if goal_sound is None and not self._have_goal:
             raise VarHipError("CollectStep.observe: no goal embedding is cached yet -- reset() or pass goal_sound "
                               "(pretext_base.py:26-32)")
         if bad is None:
             bad = self._zero_bad()
         small = [('env_reward', env_reward, self.env_reward), ('done', done, self.done), ('bad', bad, self.bad)]
-        plans = self._plans(image, extras, goal_sound, small)
+        plans = self._plans(image, extras, goal_sound, small, current_sound)
         self._stage_inputs(plans, ('env_reward', 'done', 'bad'))
         self._graphs[goal_sound is not None].replay()
         self._have_goal = True

@@ -309,6 +309,22 @@ __global__ void __launch_bounds__(256) row_dot_kernel(const float* __restrict__ 
     out[r] = s;
 }
 
+// calcReward with RLRewardSoundSound on: row_dot_kernel's sum against the goal embedding for the image rows and for the current
+// sound's rows, ONE fp32 add of the two (numpy's grouping: two float32 row sums, then their sum); c = NULL leaves row_dot_kernel's bits
+__global__ void __launch_bounds__(256) reward_dots_kernel(const float* __restrict__ a, const float* __restrict__ g, const float* __restrict__ c,
+                                                          int rows, int dim, float* __restrict__ out, float* __restrict__ out_img,
+                                                          float* __restrict__ out_snd) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    float s = 0.f, t = 0.f;
+    for (int k = 0; k < dim; ++k) s += a[(size_t)r * dim + k] * g[(size_t)r * dim + k];
+    if (c)
+        for (int k = 0; k < dim; ++k) t += c[(size_t)r * dim + k] * g[(size_t)r * dim + k];
+    out[r] = c ? s + t : s;
+    if (out_img) out_img[r] = s;
+    if (out_snd) out_snd[r] = t;
+}
+
 // inference-only forwards (save_for_bwd = 2) of at most kHead1MaxB images take the round-2 conv 1 + 2 head, at 84 x 84 and at most
 // kSmallMidB images also the small conv 3-5 kernels (img_conv_fwd.hip)
 static constexpr int kHead1MaxB = 64;
@@ -463,6 +479,20 @@ int var_row_dot(var_ctx* c, void* stream, const float* a, const float* b, int ro
     if (!a || !b || !out || rows < 1 || dim < 1 || dim > 64) { VAR_SET_ERR(c, "var_row_dot: bad argument (rows %d, dim %d)", rows, dim); return VAR_ERR_ARG; }
     SET_DEVICE(c);
     hipLaunchKernelGGL(row_dot_kernel, dim3((rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, b, rows, dim, out);
+    VAR_HIP_CHECK(c, hipGetLastError());
+    return VAR_OK;
+}
+
+int var_reward_dots(var_ctx* c, void* stream, const float* image_feat, const float* goal_feat, const float* cur_feat, int rows, int dim,
+                    float* out, float* out_img, float* out_snd) {
+    CHECK_CTX(c);
+    if (!image_feat || !goal_feat || !out || rows < 1 || dim < 1 || dim > 64) {
+        VAR_SET_ERR(c, "var_reward_dots: bad argument (rows %d, dim %d)", rows, dim);
+        return VAR_ERR_ARG;
+    }
+    SET_DEVICE(c);
+    hipLaunchKernelGGL(reward_dots_kernel, dim3((rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, image_feat, goal_feat, cur_feat, rows,
+                       dim, out, out_img, out_snd);
     VAR_HIP_CHECK(c, hipGetLastError());
     return VAR_OK;
 }

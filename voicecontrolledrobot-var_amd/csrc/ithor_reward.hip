@@ -9,6 +9,10 @@
 //       convolutions and the input projection on the gather-GEMM (gg.h), the bidirectional GRU, the three-layer head.  Up to
 //       kFusedClips clips a GRU time step is ONE launch (recurrent product of both directions on f32 MFMA + b_hh + gates + h');
 //       above that the split-K product + gate kernel pair of ithor.hip's schedule.
+//   sound-sound step (config.RLRewardSoundSound, var_ithor_reward_step_ex with current clips: EVERY environment step): the
+//       current clips take the goal clips' sound branch -- with them in one pass of 2B clips while 2B <= kFusedClips (8 envs fill
+//       the fused GRU step's 16 columns: still one launch per time step), in a pass of their own otherwise -- and the tail's last
+//       workgroup also normalises their embedding and forms <image, goal> + <current, goal>.
 // The encoder is frozen: var_ithor_reward_pack copies the parameter arena into the plan's own memory and lays conv 2..6 out in
 // MFMA A-fragment order ONCE; every step reads that snapshot, so parameters loaded later change nothing until the next pack.
 // The plan owns every buffer it touches (nothing of var_ithor_plan / var_ithor_policy_plan / var_plan is borrowed), and no
@@ -66,6 +70,7 @@ using GS3 = Geo<7, 3, 2, 2, 1, 1>;
 struct rew_state {
     RewLayout L;
     int maxB = 0;
+    int flags = 0;                           // VAR_IREW_* of the plan
     bool packed = false;
     const float* packed_from = nullptr;      // the arena of the last pack: a step with another one is refused
     float* ws = nullptr;
@@ -75,6 +80,7 @@ struct rew_state {
     float *a1 = nullptr, *p[5] = {nullptr}, *a6 = nullptr, *hid = nullptr;
     unsigned* ctr = nullptr;                 // arrivals of the tail's workgroups (rewinds itself)
     float *s[4] = {nullptr}, *GI = nullptr, *GH = nullptr, *Hb = nullptr, *hs1 = nullptr, *hs2 = nullptr, *graw = nullptr;
+    float* craw = nullptr;                   // VAR_IREW_SOUND_SOUND: the current clips' head output of a pass of their own
 };
 inline rew_state* rew(var_ctx* c) { return (rew_state*)c->irew; }
 
@@ -90,11 +96,17 @@ __global__ void __launch_bounds__(256) rw_pack_kernel(const float* __restrict__ 
 // store.  The LAST workgroup to arrive (counter pattern of heads.hip's small-batch finish: no wait anywhere) finishes the rows:
 // Linear(128,3) as four 32-unit partials per row folded in a fixed order, x / max(|x|, 1e-12) (l2norm_fwd_kernel's form), the
 // goal embedding from its raw head output when this is a goal step, and sum_d image_feat * goal_feat (row_dot_kernel's order).
+// SS (RLRewardSoundSound, a step with current clips): the same thread also normalises the row's current-sound embedding from
+// cur_raw and forms calcReward's sum in reward_dots_kernel's grouping -- reward = <image, goal> + <current, goal>, two fp32 row
+// sums and one add; the two dots go out where asked for.  SS = false is the kernel as it always was.
 constexpr int kTailWG = kHidI;
+template <bool SS>
 __global__ void __launch_bounds__(256) rw_tail_kernel(const float* __restrict__ a6, const float* __restrict__ w0, const float* __restrict__ b0,
                                                      const float* __restrict__ w1, const float* __restrict__ b1, int B, float* hid,
                                                      unsigned* ctr, const float* __restrict__ goal_raw, float* goal_feat,
-                                                     float* __restrict__ image_feat, float* __restrict__ reward) {
+                                                     float* __restrict__ image_feat, float* __restrict__ reward,
+                                                     const float* __restrict__ cur_raw, float* __restrict__ cur_feat,
+                                                     float* __restrict__ reward_img, float* __restrict__ reward_snd) {
     constexpr int N4 = kIRaw / 4, PER = (N4 + 63) / 64;       // 288 16-byte pieces of a row, 5 per lane (the last one half a wave)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = blockIdx.x;
     float4 w[PER];
@@ -166,7 +178,19 @@ __global__ void __launch_bounds__(256) rw_tail_kernel(const float* __restrict__ 
     image_feat[3 * row] = y0; image_feat[3 * row + 1] = y1; image_feat[3 * row + 2] = y2;
     float sd = 0.f;
     sd += y0 * g0; sd += y1 * g1; sd += y2 * g2;
-    reward[row] = sd;
+    if constexpr (!SS) {
+        reward[row] = sd;
+    } else {
+        const float u = cur_raw[3 * row], v = cur_raw[3 * row + 1], t = cur_raw[3 * row + 2];
+        const float cn = fmaxf(sqrtf(u * u + v * v + t * t), 1e-12f);
+        const float c0 = u / cn, c1 = v / cn, c2 = t / cn;
+        cur_feat[3 * row] = c0; cur_feat[3 * row + 1] = c1; cur_feat[3 * row + 2] = c2;
+        float ss = 0.f;
+        ss += c0 * g0; ss += c1 * g1; ss += c2 * g2;
+        reward[row] = sd + ss;
+        if (reward_img) reward_img[row] = sd;
+        if (reward_snd) reward_snd[row] = ss;
+    }
 }
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
@@ -271,11 +295,19 @@ int linear(var_ctx* c, hipStream_t s, const float* X, const float* W, const floa
     return gg_launch<DenseP<true, true, 0>, GG_KC, false>(c, s, p);
 }
 
-// the sound branch of ithor.hip's fp32 forward for B goal clips -> st->graw (B,3), the head's output before F.normalize
-int goal_branch(var_ctx* c, hipStream_t s, rew_state* st, const float* goal, int B) {
+// the sound branch of ithor.hip's fp32 forward for a set of n clips -> out (B,3), the head's output before F.normalize.  With
+// `more` (a second set of n clips, 2n <= kFusedClips) both sets go through in ONE pass of B = 2n clips, `more` behind `clips` in
+// every buffer: conv 1 runs per set (each set is its caller's own array), every later layer once.  No kernel below mixes clips
+// (the gather-GEMMs run unsplit, a clip is one MFMA column of the fused GRU step), so a clip's rows have the bits of a pass
+// without the other set.
+int goal_branch(var_ctx* c, hipStream_t s, rew_state* st, const float* clips, const float* more, int n, float* out) {
     const RewLayout& L = st->L;
     const float* P = st->frozen;
-    RUN((snd_conv<GS1, false>(c, s, conv_dims(B, 1, kT, kF, 64, 11, 11, 2, 2, 5, 5), goal, P + L.sw[0], P + L.sb[0], st->s[1])));
+    const int B = more ? 2 * n : n;
+    RUN((snd_conv<GS1, false>(c, s, conv_dims(n, 1, kT, kF, 64, 11, 11, 2, 2, 5, 5), clips, P + L.sw[0], P + L.sb[0], st->s[1])));
+    if (more)
+        RUN((snd_conv<GS1, false>(c, s, conv_dims(n, 1, kT, kF, 64, 11, 11, 2, 2, 5, 5), more, P + L.sw[0], P + L.sb[0],
+                                  st->s[1] + (long)n * 64 * 300 * 20)));
     RUN((snd_conv<GS2, false>(c, s, conv_dims(B, 64, 300, 20, 64, 11, 5, 2, 2, 5, 5), st->s[1], P + L.sw[1], P + L.sb[1], st->s[2])));
     RUN((snd_conv<GS3, true>(c, s, conv_dims(B, 64, 150, 13, 64, 7, 3, 2, 2, 1, 1), st->s[2], P + L.sw[2], P + L.sb[2], st->s[3])));
     const int rows = B * kSeq;
@@ -314,7 +346,7 @@ int goal_branch(var_ctx* c, hipStream_t s, rew_state* st, const float* goal, int
     const float* sraw = st->Hb + (kSeq & 1) * slot;
     RUN(linear(c, s, sraw, P + L.sh_w0, P + L.sh_b0, st->hs1, B, kSRaw, 128, 1));
     RUN(linear(c, s, st->hs1, P + L.sh_w1, P + L.sh_b1, st->hs2, B, 128, 64, 1));
-    RUN(linear(c, s, st->hs2, P + L.sh_w2, P + L.sh_b2, st->graw, B, 64, 3, 0));
+    RUN(linear(c, s, st->hs2, P + L.sh_w2, P + L.sh_b2, out, B, 64, 3, 0));
     return VAR_OK;
 }
 }  // namespace
@@ -330,7 +362,7 @@ void ithor_reward_free(var_ctx* c) {
 // var_debug_buffer's "irew_" names, lengths those of the PLAN's batch (a step of B rows fills the first B rows of each, except
 // gi (dir stride B * 73 * 1536) and gh (slab stride 2 * B * 1536, dir stride B * 1536), which follow B; the two hb slots are
 // maxB * 1024 apart): a1, p1..p4, a6 (maxB, 1152), hid (maxB, 128), s1, s2, s3 (clip, 73, 448), gi, gh, hb, hs1, hs2, graw,
-// frozen (the parameter snapshot)
+// craw (a plan with VAR_IREW_SOUND_SOUND; empty otherwise), frozen (the parameter snapshot)
 int ithor_reward_debug_buffer(var_ctx* c, const char* name, void** ptr, long* nfloats) {
     rew_state* st = rew(c);
     if (!st) { VAR_SET_ERR(c, "var_debug_buffer: no var_ithor_reward_plan"); return VAR_ERR_PLAN; }
@@ -340,7 +372,8 @@ int ithor_reward_debug_buffer(var_ctx* c, const char* name, void** ptr, long* nf
         {"p3", st->p[3], B * 64 * 12 * 12}, {"p4", st->p[4], B * 128 * 6 * 6}, {"a6", st->a6, B * kIRaw}, {"hid", st->hid, B * kHidI},
         {"s1", st->s[1], B * 64 * 300 * 20}, {"s2", st->s[2], B * 64 * 150 * 13}, {"s3", st->s[3], B * kSeq * kGin},
         {"gi", st->GI, 2 * B * kSeq * kG3}, {"gh", st->GH, (long)kRecSplit * 2 * B * kG3}, {"hb", st->Hb, 2 * B * kSRaw},
-        {"hs1", st->hs1, B * 128}, {"hs2", st->hs2, B * 64}, {"graw", st->graw, B * 3}, {"frozen", st->frozen, st->L.total},
+        {"hs1", st->hs1, B * 128}, {"hs2", st->hs2, B * 64}, {"graw", st->graw, B * 3}, {"craw", st->craw, st->craw ? B * 3 : 0},
+        {"frozen", st->frozen, st->L.total},
     };
     for (const auto& e : tab)
         if (!strcmp(name, e.name)) { *ptr = e.p; *nfloats = e.n; return VAR_OK; }
@@ -350,8 +383,11 @@ int ithor_reward_debug_buffer(var_ctx* c, const char* name, void** ptr, long* nf
 
 extern "C" {
 
-int var_ithor_reward_plan(var_ctx* c, int max_batch, int img_hw) {
+int var_ithor_reward_plan(var_ctx* c, int max_batch, int img_hw) { return var_ithor_reward_plan_ex(c, max_batch, img_hw, 0); }
+
+int var_ithor_reward_plan_ex(var_ctx* c, int max_batch, int img_hw, int flags) {
     if (!c) return VAR_ERR_ARG;
+    if (flags & ~VAR_IREW_SOUND_SOUND) { VAR_SET_ERR(c, "var_ithor_reward_plan_ex: unknown flags 0x%x", flags); return VAR_ERR_ARG; }
     if (img_hw != 96) {
         VAR_SET_ERR(c, "var_ithor_reward_plan: image side %d, the band kernels take 96 (use var_ithor_encoder_fwd otherwise)", img_hw);
         return VAR_ERR_ARG;
@@ -367,9 +403,17 @@ int var_ithor_reward_plan(var_ctx* c, int max_batch, int img_hw) {
     }
     VAR_HIP_CHECK(c, hipSetDevice(c->device));
     rew_state* st = rew(c);
-    if (st && st->maxB >= max_batch) return VAR_OK;
+    // sound-sound: the goal and the current clips of up to kFusedClips / 2 envs share one pass of the sound branch, so the plan is
+    // made for that many rows (throughout: the image buffers of 16 rows are under 30 MB, and every irew_ length stays one batch)
+    if (flags & VAR_IREW_SOUND_SOUND) {
+        const int both = 2 * max_batch < kFusedClips ? 2 * max_batch : kFusedClips;
+        max_batch = max_batch > both ? max_batch : both;
+    }
+    if (st && st->maxB >= max_batch && (st->flags & flags) == flags) return VAR_OK;
     if (st) {      // retire (do not free) the superseded block: a captured reward graph may still replay on it
         if (st->ws) { int rc = retire_block(c, st->ws); if (rc != VAR_OK) return rc; }
+        max_batch = max_batch > st->maxB ? max_batch : st->maxB;      // (only grows, whatever made it grow)
+        flags |= st->flags;
         delete st;
         c->irew = nullptr;
     }
@@ -377,6 +421,7 @@ int var_ithor_reward_plan(var_ctx* c, int max_batch, int img_hw) {
     c->irew = st;
     st->L = L;
     st->maxB = max_batch;
+    st->flags = flags;
     st->pack = make_pack_desc(kCh + 1, st->L.iw + 1, 5);          // conv 2..6
     const long B = max_batch;
     long total = 0;
@@ -388,6 +433,7 @@ int var_ithor_reward_plan(var_ctx* c, int max_batch, int img_hw) {
     const long os1 = take(B * 64 * 300 * 20), os2 = take(B * 64 * 150 * 13), os3 = take(B * kSeq * kGin);
     const long oGI = take(2 * B * kSeq * kG3), oGH = take((long)kRecSplit * 2 * B * kG3), oHb = take(2 * B * kSRaw);
     const long ohs1 = take(B * 128), ohs2 = take(B * 64), ograw = take(B * 3);
+    const long ocraw = (flags & VAR_IREW_SOUND_SOUND) ? take(B * 3) : -1;
     VAR_HIP_CHECK(c, hipMalloc((void**)&st->ws, (size_t)total * sizeof(float)));
     float* w = st->ws;
     st->frozen = w + ofz; st->wpk = (c3f::f32x4*)(w + owpk);
@@ -395,6 +441,7 @@ int var_ithor_reward_plan(var_ctx* c, int max_batch, int img_hw) {
     st->a6 = w + oa6; st->hid = w + ohid; st->ctr = (unsigned*)(w + octr);
     st->s[1] = w + os1; st->s[2] = w + os2; st->s[3] = w + os3;
     st->GI = w + oGI; st->GH = w + oGH; st->Hb = w + oHb; st->hs1 = w + ohs1; st->hs2 = w + ohs2; st->graw = w + ograw;
+    st->craw = ocraw >= 0 ? w + ocraw : nullptr;
     VAR_HIP_CHECK(c, hipMemset(st->ctr, 0, 64 * sizeof(float)));
     VAR_HIP_CHECK(c, hipDeviceSynchronize());
     return VAR_OK;
@@ -417,12 +464,25 @@ int var_ithor_reward_pack(var_ctx* c, void* stream, const float* params) {
 
 int var_ithor_reward_step(var_ctx* c, void* stream, const float* params, const void* image, int image_is_u8, long image_bstride,
                           const float* goal_mfcc, int B, float* image_feat, float* goal_feat, float* reward) {
+    return var_ithor_reward_step_ex(c, stream, params, image, image_is_u8, image_bstride, goal_mfcc, nullptr, B, image_feat, goal_feat,
+                                    nullptr, reward, nullptr, nullptr);
+}
+
+int var_ithor_reward_step_ex(var_ctx* c, void* stream, const float* params, const void* image, int image_is_u8, long image_bstride,
+                             const float* goal_mfcc, const float* cur_mfcc, int B, float* image_feat, float* goal_feat, float* cur_feat,
+                             float* reward, float* reward_img, float* reward_snd) {
     if (!c) return VAR_ERR_ARG;
     rew_state* st = rew(c);
     if (!st || B > st->maxB) { VAR_SET_ERR(c, "var_ithor_reward_step: var_ithor_reward_plan(%d, 96) first", B); return VAR_ERR_PLAN; }
-    if (!params || !image || !image_feat || !goal_feat || !reward || B < 1) {
+    if (!params || !image || !image_feat || !goal_feat || !reward || B < 1 || (cur_mfcc && !cur_feat)) {
         VAR_SET_ERR(c, "var_ithor_reward_step: NULL argument or B < 1");
         return VAR_ERR_ARG;
+    }
+    // goal and current clips share one pass where both fit the fused GRU step's column block
+    const bool merged = goal_mfcc && cur_mfcc && 2 * B <= kFusedClips;
+    if (cur_mfcc && (!(st->flags & VAR_IREW_SOUND_SOUND) || (merged && 2 * B > st->maxB))) {
+        VAR_SET_ERR(c, "var_ithor_reward_step_ex: var_ithor_reward_plan_ex(%d, 96, VAR_IREW_SOUND_SOUND) first", B);
+        return VAR_ERR_PLAN;
     }
     if (image_bstride < 3L * 96 * 96) {
         VAR_SET_ERR(c, "var_ithor_reward_step: image stride %ld < 3*96*96", image_bstride);
@@ -445,9 +505,22 @@ int var_ithor_reward_step(var_ctx* c, void* stream, const float* params, const v
     RUN(c3f::launch<IthorC4>(c, s, st->p[2], st->wpk + d.wp_off[2], P + L.ib[3], st->p[3], B));
     RUN(c3f::launch<IthorC5>(c, s, st->p[3], st->wpk + d.wp_off[3], P + L.ib[4], st->p[4], B));
     RUN(c3f::launch_small<IthorC6>(c, s, st->p[4], st->wpk + d.wp_off[4], P + L.ib[5], st->a6, B));
-    if (goal_mfcc) RUN(goal_branch(c, s, st, goal_mfcc, B));
-    hipLaunchKernelGGL(rw_tail_kernel, dim3(kTailWG), dim3(256), 0, s, (const float*)st->a6, P + L.ih_w0, P + L.ih_b0, P + L.ih_w1, P + L.ih_b1,
-                       B, st->hid, st->ctr, goal_mfcc ? (const float*)st->graw : (const float*)nullptr, goal_feat, image_feat, reward);
+    const float* craw = nullptr;
+    if (merged) {
+        RUN(goal_branch(c, s, st, goal_mfcc, cur_mfcc, B, st->graw));
+        craw = st->graw + 3 * B;
+    } else {
+        if (goal_mfcc) RUN(goal_branch(c, s, st, goal_mfcc, nullptr, B, st->graw));
+        if (cur_mfcc) { RUN(goal_branch(c, s, st, cur_mfcc, nullptr, B, st->craw)); craw = st->craw; }
+    }
+    const float* graw = goal_mfcc ? (const float*)st->graw : (const float*)nullptr;
+    if (cur_mfcc)
+        hipLaunchKernelGGL(rw_tail_kernel<true>, dim3(kTailWG), dim3(256), 0, s, (const float*)st->a6, P + L.ih_w0, P + L.ih_b0, P + L.ih_w1,
+                           P + L.ih_b1, B, st->hid, st->ctr, graw, goal_feat, image_feat, reward, craw, cur_feat, reward_img, reward_snd);
+    else
+        hipLaunchKernelGGL(rw_tail_kernel<false>, dim3(kTailWG), dim3(256), 0, s, (const float*)st->a6, P + L.ih_w0, P + L.ih_b0, P + L.ih_w1,
+                           P + L.ih_b1, B, st->hid, st->ctr, graw, goal_feat, image_feat, reward, (const float*)nullptr, (float*)nullptr,
+                           (float*)nullptr, (float*)nullptr);
     AC_CHECK(c);
     return VAR_OK;
 }

@@ -5,7 +5,9 @@ Mirrors what the reference's vectorised-env wrapper does around the pretext mode
 plumbing: Envs/vec_env/vec_pretext_normalize.py:82-101 (getEmbeddings / calcReward), :47-59 (discounted-return
 normalisation with clipping) and Envs/vec_env/running_mean_std.py:4-35 (streaming mean / variance).  The encoder
 forward is the HIP path (VARPretextNet.forward); the rest is host arithmetic on (num_envs,) arrays in float64,
-as in the reference.
+as in the reference.  IntrinsicReward(model, sound_sound=True) is config.RLRewardSoundSound: the current sound of every step
+is embedded too and <current_sound_feat, goal_sound_feat> joins the reward, on the eager pair embeddings() / reward() and on the
+captured step().
 """
 import numpy as np
 import torch
@@ -93,10 +95,17 @@ class IntrinsicReward:
         For an IthorVARPretextNet the step is var_ithor_reward_step (96 x 96 images, at most 64 envs): the arena is
         snapshotted and its convolutions packed once here, so the graphs follow the weights the model had at this call
         until capture() is called again.  The goal embedding is cached for the WHOLE batch (pretext_base.py:26-32:
-        every env resets at the same time); step(image, None) before any goal step raises."""
+        every env resets at the same time); step(image, None) before any goal step raises.
+
+        With sound_sound (config.RLRewardSoundSound) both graphs also embed the current sound of every step and the reward
+        is calcReward's <image_feat, goal_feat> + <current_sound_feat, goal_feat> (var_reward_dots' grouping).  Further
+        static buffers, as attributes: current_sound (B,) + sound_dim, cur_feat (B,3), img_sound_dot and sound_sound_dot
+        (B,).  The Kuka encoder takes the current sound as var_arm_encoder_fwd's mfcc_neg and var_reward_dots follows the
+        forward (var_set_reward_dot is not armed); the iTHOR encoder is var_ithor_reward_step_ex."""
         from ._lib import Context, current_stream_handle, new_graph, ptr
         m = self.model
         from .ithor import IthorVARPretextNet
+        self.current_sound = None                # (set by a capture with sound_sound)
         if isinstance(m, IthorVARPretextNet):
             return self._capture_ithor(batch)
         flat = m.flat_parameters()
@@ -111,10 +120,24 @@ class IntrinsicReward:
         self._image_feat = torch.zeros((B, 3), device=dev)
         self._goal_feat = torch.zeros((B, 3), device=dev)
         self._reward = torch.zeros((B,), device=dev)
+        ss = bool(self.sound_sound)
+        if ss:
+            self._sound_sound_buffers(B, (1, 100, 40), dev)
         w = m.hip_weights(c, force=True)        # the frozen model's own packed image; the graphs keep its address
 
         def body(with_goal):
             w.bind()
+            if ss:
+                # the current sound rides as the forward's negative clip; both dots and their sum are one launch behind it
+                c.check(c.lib.var_arm_encoder_fwd(c.handle, current_stream_handle(), ptr(flat), ptr(self._img), 1,
+                                                  self._img.stride(0), ptr(self._goal) if with_goal else None,
+                                                  ptr(self.current_sound), B, hw, ptr(self._image_feat),
+                                                  ptr(self._goal_feat) if with_goal else None, ptr(self.cur_feat),
+                                                  None, None, 2), "var_arm_encoder_fwd")
+                c.check(c.lib.var_reward_dots(c.handle, current_stream_handle(), ptr(self._image_feat), ptr(self._goal_feat),
+                                              ptr(self.cur_feat), B, self._image_feat.shape[1], ptr(self._reward),
+                                              ptr(self.img_sound_dot), ptr(self.sound_sound_dot)), "var_reward_dots")
+                return
             if not with_goal:
                 # the goal embedding is cached: the forward itself leaves <image_feat, goal_feat> (var_set_reward_dot)
                 c.check(c.lib.var_set_reward_dot(c.handle, ptr(self._goal_feat), ptr(self._reward)), "var_set_reward_dot")
@@ -153,7 +176,8 @@ class IntrinsicReward:
             raise VarHipError("parameter arena does not match var_ithor_param_count()")
         hw = m.config.img_dim[1]
         B = int(batch)
-        c.check(c.lib.var_ithor_reward_plan(c.handle, B, int(hw)), "var_ithor_reward_plan")
+        ss = bool(self.sound_sound)
+        c.check(c.lib.var_ithor_reward_plan_ex(c.handle, B, int(hw), int(ss)), "var_ithor_reward_plan_ex")
         c.check(c.lib.var_ithor_reward_pack(c.handle, current_stream_handle(), ptr(flat)), "var_ithor_reward_pack")
         self._B = B
         self._ithor = True
@@ -163,8 +187,17 @@ class IntrinsicReward:
         self._image_feat = torch.zeros((B, 3), device=dev)
         self._goal_feat = torch.zeros((B, 3), device=dev)
         self._reward = torch.zeros((B,), device=dev)
+        if ss:
+            self._sound_sound_buffers(B, tuple(m.config.sound_dim), dev)
 
         def body(with_goal):
+            if ss:
+                c.check(c.lib.var_ithor_reward_step_ex(c.handle, current_stream_handle(), ptr(flat), ptr(self._img), 1,
+                                                       self._img.stride(0), ptr(self._goal) if with_goal else None,
+                                                       ptr(self.current_sound), B, ptr(self._image_feat), ptr(self._goal_feat),
+                                                       ptr(self.cur_feat), ptr(self._reward), ptr(self.img_sound_dot),
+                                                       ptr(self.sound_sound_dot)), "var_ithor_reward_step_ex")
+                return
             c.check(c.lib.var_ithor_reward_step(c.handle, current_stream_handle(), ptr(flat), ptr(self._img), 1,
                                                 self._img.stride(0), ptr(self._goal) if with_goal else None, B,
                                                 ptr(self._image_feat), ptr(self._goal_feat), ptr(self._reward)),
@@ -184,8 +217,31 @@ class IntrinsicReward:
         torch.cuda.current_stream().wait_stream(side)
         return self
 
-    def _step_ithor(self, image_u8, goal_sound):
+    def _sound_sound_buffers(self, B, sound_dim, dev):
+        self.current_sound = torch.zeros((B,) + tuple(sound_dim), dtype=torch.float32, device=dev)
+        self.cur_feat = torch.zeros((B, 3), device=dev)
+        self.img_sound_dot = torch.zeros((B,), device=dev)
+        self.sound_sound_dot = torch.zeros((B,), device=dev)
+
+    def _check_current(self, current_sound, cuda_only):
+        """The current sound of a sound-sound step as a tensor, refused before anything is copied or replayed."""
         from ._lib import VarHipError
+        if current_sound is None:
+            raise VarHipError("IntrinsicReward.step: sound_sound is on -- every step needs current_sound "
+                              "(vec_pretext_normalize.py:82-95)")
+        current_sound = torch.as_tensor(current_sound)
+        if cuda_only and not current_sound.is_cuda:
+            raise VarHipError("IntrinsicReward.step: current_sound must be a CUDA tensor (no CPU fallback)")
+        if tuple(current_sound.shape) != tuple(self.current_sound.shape):
+            raise VarHipError(f"IntrinsicReward.step: current_sound shape {tuple(current_sound.shape)} is not "
+                              f"{tuple(self.current_sound.shape)}")
+        return current_sound
+
+    def _step_ithor(self, image_u8, goal_sound, current_sound=None):
+        from ._lib import VarHipError
+        ss = getattr(self, "current_sound", None) is not None
+        if ss:
+            current_sound = self._check_current(current_sound, True)
         image_u8 = torch.as_tensor(image_u8)
         if not image_u8.is_cuda:
             raise VarHipError("IntrinsicReward.step: image must be a CUDA tensor (no CPU fallback)")
@@ -205,15 +261,23 @@ class IntrinsicReward:
         if goal_sound is not None:
             self._goal.copy_(goal_sound, non_blocking=True)
             self._have_goal = True
+        if ss:
+            self.current_sound.copy_(current_sound, non_blocking=True)
         self._graphs[goal_sound is not None].replay()
         return self._image_feat, self._goal_feat, self._reward
 
-    def step(self, image_u8, goal_sound=None):
+    def step(self, image_u8, goal_sound=None, current_sound=None):
         """One env step of `batch` envs: copies the observations into the static buffers and replays the graph.
-        Returns device tensors (image_feat (B,3), goal_feat (B,3), <image_feat, goal_feat> (B,)); they are
-        overwritten by the next step."""
+        Returns device tensors (image_feat (B,3), goal_feat (B,3), reward (B,)); they are overwritten by the next step.
+        reward is <image_feat, goal_feat>; captured with sound_sound it is that plus <cur_feat, goal_feat> (the two terms
+        stay in img_sound_dot / sound_sound_dot, the current sound's embedding in cur_feat) and every step needs
+        current_sound -- without it the step raises before anything is copied or replayed.  Captured without sound_sound,
+        current_sound is ignored, as embeddings() ignores it."""
         if getattr(self, "_ithor", False):
-            return self._step_ithor(image_u8, goal_sound)
+            return self._step_ithor(image_u8, goal_sound, current_sound)
+        if getattr(self, "current_sound", None) is not None:
+            current_sound = self._check_current(current_sound, False)
+            self.current_sound.copy_(current_sound, non_blocking=True)
         self._img.copy_(torch.as_tensor(image_u8), non_blocking=True)
         if goal_sound is not None:
             self._goal.copy_(torch.as_tensor(goal_sound), non_blocking=True)
