@@ -115,6 +115,21 @@ int var_row_dot(var_ctx* ctx, void* stream, const float* a, const float* b, int 
 int var_reward_dots(var_ctx* ctx, void* stream, const float* image_feat, const float* goal_feat,
                     const float* cur_feat /* NULL: no second term */, int rows, int dim, float* out,
                     float* out_img /* may be NULL */, float* out_snd /* may be NULL */);
+/* var_reward_dots with the sound embeddings served from a device clip table (table_rows x dim f32: a clip's embedding is a constant
+ * of the frozen checkpoint and the clip, Envs/audioLoader.py:166-237 draws from a finite, unaugmented pool), ONE launch, a thread
+ * per row.  It follows an image-only var_arm_encoder_fwd(..., save_for_bwd = 2); var_set_reward_dot is not armed on this path.
+ *   goal_ids (rows) i32 on the device | NULL: id g >= 0 takes table[g] and writes it to goal_feat[r] (the policy's
+ *       goal_sound_feat); g == -1 reads goal_feat[r], the embedding cached FOR THAT ROW; NULL = every row -1.
+ *   cur_ids (rows) i32 on the device | NULL: cur_feat[r] = table[c] and out = a + b, var_reward_dots' grouping; NULL: out = a,
+ *       cur_feat untouched, out_snd (where given) 0.
+ * An id outside its range (goal < -1 or >= table_rows; current < 0 or >= table_rows) is never turned into an address: that row's
+ * out, out_img, out_snd and cur_feat are NaN and its goal_feat stays as it was; other rows are unaffected.  The ids are read on
+ * the device, so one captured launch serves goal steps, cached steps and staggered resets.  VAR_ERR_ARG, nothing launched:
+ * image_feat / table / goal_feat / out NULL, table_rows < 1, cur_ids without cur_feat, rows < 1, dim outside 1..64. */
+int var_reward_dots_ids(var_ctx* ctx, void* stream, const float* image_feat, const float* table, int table_rows,
+                        const int* goal_ids /* | NULL */, const int* cur_ids /* | NULL */, float* goal_feat /* in/out */,
+                        float* cur_feat /* out | NULL */, int rows, int dim, float* out, float* out_img /* may be NULL */,
+                        float* out_snd /* may be NULL */);
 /* Arms the NEXT var_arm_encoder_fwd with an image: it also leaves reward_out[b] = <image_feat[b], goal_feat[b]> (3 floats per
  * row, var_row_dot's sum) -- the intrinsic reward of VAR/pretext_base.py's calcReward.  Where the image head is a launch of its
  * own that finishes the embeddings (save_for_bwd = 2, 84 x 84, at most 16 rows: the RL stage's envs) the dot rides in that launch
@@ -884,6 +899,37 @@ int var_ithor_reward_step(var_ctx* ctx, void* stream, const float* params,
                           const void* image, int image_is_u8, long image_bstride,
                           const float* goal_mfcc, int B,
                           float* image_feat, float* goal_feat, float* reward);
+/* The sound embeddings from a device clip table.  The env's sounds come from a finite, unaugmented pool (Envs/audioLoader.py:
+ * 166-237: a stored clip picked by index, the all-zero matrix when nothing is heard) and the encoder is frozen, so a clip's
+ * embedding is a constant of (checkpoint, clip): embed the pool once, then a step gathers rows by id instead of running the
+ * sound branch.
+ *   var_ithor_reward_embed  mfcc (n,1,600,40) f32 -> out (n,3), any n >= 1, with the packed snapshot: the sound branch over the
+ *       plan's own buffers in passes of at most min(16, plan rows) clips -- always the fused one-launch GRU step -- and after
+ *       each pass one small kernel that normalises the pass's head outputs with the tail's expression.  Needs a plan and a pack,
+ *       params == the packed arena (VAR_ERR_PLAN / VAR_ERR_STATE as var_ithor_reward_step; mfcc / out NULL or n < 1:
+ *       VAR_ERR_ARG); a refused call launches nothing.  No allocation; capturable.  Row i has the bits var_ithor_reward_step_ex
+ *       writes to cur_feat and var_ithor_reward_step to goal_feat for the same clip at any B up to 16 clips a pass, whichever
+ *       clips share its pass: no kernel of the branch mixes clips.  Launches: 81 per pass.
+ *   var_ithor_reward_step_ids  the image stack's six launches + ONE tail, 7 kernels on every kind of step; the tail's finishing
+ *       thread of a row gathers from table (table_rows, 3) instead of normalising head outputs.  goal_ids (B) i32 on the
+ *       device | NULL: id g >= 0 takes table[g] and writes it to goal_feat[row]; g == -1 reads goal_feat[row], the embedding
+ *       cached for THAT env (an env that starts an episode alone gets its new goal without the others re-sending theirs); NULL
+ *       = every row -1.  cur_ids (B) i32 on the device | NULL: cur_feat[row] = table[c], reward = <image, goal> + <current,
+ *       goal> in var_reward_dots' grouping, reward_img / reward_snd where given; NULL: var_ithor_reward_step's image-only
+ *       bits, cur_feat / reward_img / reward_snd untouched.  An id outside its range (goal < -1 or >= table_rows; current < 0
+ *       or >= table_rows) is never turned into an address: that row's image_feat, cur_feat and rewards are NaN, its goal_feat
+ *       stays as it was, other rows are unaffected.  The ids are read on the device: one captured graph serves goal steps,
+ *       image-only steps and staggered resets.  Any plan serves (no VAR_IREW_SOUND_SOUND needed: no sound pass is reserved).
+ *       VAR_ERR_PLAN / VAR_ERR_STATE / VAR_ERR_ARG as var_ithor_reward_step; also VAR_ERR_ARG: cur_ids without cur_feat, table
+ *       NULL, table_rows < 1.  A failed call launches nothing. */
+int var_ithor_reward_embed(var_ctx* ctx, void* stream, const float* params, const float* mfcc /* (n,1,600,40) */, int n,
+                           float* out /* (n,3) */);
+int var_ithor_reward_step_ids(var_ctx* ctx, void* stream, const float* params,
+                              const void* image, int image_is_u8, long image_bstride,
+                              const float* table, int table_rows,
+                              const int* goal_ids /* (B) device | NULL */, const int* cur_ids /* (B) device | NULL */, int B,
+                              float* image_feat, float* goal_feat, float* cur_feat, float* reward,
+                              float* reward_img /* | NULL */, float* reward_snd /* | NULL */);
 
 /* The iTHOR/FSC audio front-end: python_speech_features.mfcc as called at Envs/audioLoader.py:158-161 (pre-emphasis
  * .97, 400/160 frames with a zero-padded tail, np.hamming, |rfft_512|^2/512, 40 triangles, log, orthonormal DCT-II,

@@ -16,7 +16,7 @@ from .comm import RcclComm  # noqa: F401
 from .trainer import VARTrainer, train_representation, train_representation_from_pool, multistep_lr  # noqa: F401
 from .data import SyntheticTripletPool, TripletPool, choose_negative_id, load_wav_clips, process_sound_feat  # noqa: F401
 from .ops import inbatch_contrastive_loss, mfcc, mfcc_psf, triplet_margin_loss  # noqa: F401
-from .reward import IntrinsicReward, ReturnNormalizer, RunningMeanStd  # noqa: F401
+from .reward import ClipTable, IntrinsicReward,ReturnNormalizer, RunningMeanStd  # noqa: F401
 from .rollout import PPO, RolloutStorage, ppo_head_linear, ppo_loss  # noqa: F401
 from .update_step import UpdateStep  # noqa: F401
 from .collect import CollectStep, DeviceReturnNormalizer  # noqa: F401

@@ -135,6 +135,9 @@ _SIGNATURES = {
     "var_ithor_reward_plan_ex": (_i, [_vp, _i, _i, _i]),
     "var_ithor_reward_step_ex": (_i, [_vp, _vp, _vp, _vp, _i, _l, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "var_reward_dots": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "var_reward_dots_ids": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "var_ithor_reward_embed": (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
+    "var_ithor_reward_step_ids": (_i, [_vp, _vp, _vp, _vp, _i, _l, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "var_mfcc_psf": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "var_ithor_param_count": (_i, []),
     "var_ithor_plan": (_i, [_vp, _i, _i]),

@@ -166,12 +166,20 @@ class CollectStep:
     extras: {'robot_pose': (N,2)} (Kuka) / {'occupancy': (N,1,9,9)} (iTHOR).  Host arrays go through pinned staging buffers with non-blocking copies (an event guards the block's reuse); device tensors are copied, or
     used in place when they ARE the buffers (act_step.obs[...], self.env_reward, self.done, self.bad, self.goal_sound,
     self.current_sound).
-    norm: the DeviceReturnNormalizer (reward, bad_masks, orig_reward, episode, state()); episode_stats() reads the episode block."""
+    norm: the DeviceReturnNormalizer (reward, bad_masks, orig_reward, episode, state()); episode_stats() reads the episode block.
 
-    def __init__(self, reward, act_step, rollouts, gamma=0.99, cliprew=10., epsilon=1e-8, normalize=True):
+    clip_table (IntrinsicReward.build_clip_table of the same encoder): the sounds arrive as clip indices, not feature arrays --
+    reset(image, extras, goal_ids=...), observe(..., goal_ids=None, current_ids=None); a goal id of -1 keeps THAT env's cached
+    goal, so an env that starts an episode alone gets its new goal alone.  The replay holds no sound branch (iTHOR:
+    var_ithor_reward_step_ids, 7 kernels; Kuka: an image-only var_arm_encoder_fwd + var_reward_dots_ids) and is captured once --
+    the ids are read on the device -- beside the reset's; host ids ride in the small pinned block (2 * 4N bytes more, still
+    one copy) and are range-checked before anything is staged; self.goal_ids / self.current_ids are the device buffers.
+    Without clip_table everything is as described above."""
+
+    def __init__(self, reward, act_step, rollouts, gamma=0.99, cliprew=10., epsilon=1e-8, normalize=True, clip_table=None):
         from .actor_critic import ActStep
         from .ithor import IthorVARPretextNet
-        from .reward import IntrinsicReward
+        from .reward import ClipTable, IntrinsicReward
         from .rollout import RolloutStorage
         if not isinstance(reward, IntrinsicReward) or not isinstance(act_step, ActStep) or not isinstance(rollouts, RolloutStorage):
             raise VarHipError("CollectStep(reward: IntrinsicReward, act_step: ActStep, rollouts: RolloutStorage)")
@@ -198,17 +206,36 @@ class CollectStep:
         self._segs = (MoveAtSeg * len(self._table))(*(s for _, s in self._table))
         obs = act_step.obs
         self._extra = [k for k in obs if k not in ('image', 'image_feat', 'goal_sound_feat')]
-        self.goal_sound = torch.zeros((N,) + tuple(m.config.sound_dim), dtype=torch.float32, device=dev)
+        table = self.clip_table = clip_table
+        if table is not None:
+            if not isinstance(table, ClipTable) or table.dim != 3 or table.feat.device != dev:
+                raise VarHipError("CollectStep: clip_table must be a ClipTable of this encoder (IntrinsicReward.build_clip_table)")
+            table.check(m)
+        else:
+            self.goal_sound = torch.zeros((N,) + tuple(m.config.sound_dim), dtype=torch.float32, device=dev)
         self.dot = torch.zeros(N, device=dev)
         ss = self.sound_sound = bool(getattr(reward, "sound_sound", False))
         if ss:                                                   # RLRewardSoundSound: O['current_sound'] of every step, and what it adds
-            self.current_sound = torch.zeros_like(self.goal_sound)
+            if table is None:
+                self.current_sound = torch.zeros_like(self.goal_sound)
             self.cur_feat = torch.zeros(N, 3, device=dev)
             self.dot_img, self.dot_snd = torch.zeros(N, device=dev), torch.zeros(N, device=dev)
-        # env_reward f64 | done u8 | bad u8: one device block, one staging copy
-        self._small = torch.zeros(8 * N + 2 * N, dtype=torch.uint8, device=dev)
+        # env_reward f64 | done u8 | bad u8: one device block, one staging copy; with a clip table the goal and the current ids
+        # (i32 each) ride in it behind env_reward
+        ids = 8 * N if table is not None else 0
+        self._small = torch.zeros(8 * N + ids + 2 * N, dtype=torch.uint8, device=dev)
         self.env_reward = self._small[:8 * N].view(torch.float64)
-        self.done, self.bad = self._small[8 * N:9 * N], self._small[9 * N:]
+        self.done, self.bad = self._small[8 * N + ids:9 * N + ids], self._small[9 * N + ids:]
+        self._small_offs = {'env_reward': 0, 'done': 8 * N + ids, 'bad': 9 * N + ids}
+        self._n_small = 3 if table is None else 4 + int(ss)      # what an observe() stages there: all from the host = one copy
+        if table is not None:
+            self.goal_ids = self._small[8 * N:12 * N].view(torch.int32)
+            self.current_ids = self._small[12 * N:16 * N].view(torch.int32)
+            self._small_offs.update(goal_ids=8 * N, current_ids=12 * N)
+            self.goal_ids.fill_(-1)
+            self.current_ids.fill_(table.silent)
+            self._goal_set = np.zeros(N, bool)                   # per env: has a goal embedding been cached?
+            self._keep_ids = np.full(N, -1, np.int32)
         image, img_feat, goal_feat = obs['image'], obs['image_feat'], obs['goal_sound_feat']
         is_u8 = int(image.dtype == torch.uint8)
         ithor = isinstance(m, IthorVARPretextNet)
@@ -220,6 +247,15 @@ class CollectStep:
             c.check(c.lib.var_ithor_reward_pack(c.handle, current_stream_handle(), ptr(flat)), "var_ithor_reward_pack")
 
             def encoder(with_goal, with_cur=ss):
+                if table is not None:                            # 7 kernels, whatever the ids say
+                    cur = with_cur and ss
+                    c.check(c.lib.var_ithor_reward_step_ids(c.handle, current_stream_handle(), ptr(flat), ptr(image), is_u8,
+                                                            image.stride(0), ptr(table.feat), table.rows + 1, ptr(self.goal_ids),
+                                                            ptr(self.current_ids) if cur else None, N, ptr(img_feat), ptr(goal_feat),
+                                                            ptr(self.cur_feat) if cur else None, ptr(self.dot),
+                                                            ptr(self.dot_img) if cur else None, ptr(self.dot_snd) if cur else None),
+                            "var_ithor_reward_step_ids")
+                    return
                 if with_cur:
                     c.check(c.lib.var_ithor_reward_step_ex(c.handle, current_stream_handle(), ptr(flat), ptr(image), is_u8,
                                                            image.stride(0), ptr(self.goal_sound) if with_goal else None,
@@ -235,6 +271,16 @@ class CollectStep:
 
             def encoder(with_goal, with_cur=ss):
                 w.bind()
+                if table is not None:                            # image only; the sounds' embeddings are gathered by the dots' launch
+                    cur = with_cur and ss
+                    c.check(c.lib.var_arm_encoder_fwd(c.handle, current_stream_handle(), ptr(flat), ptr(image), is_u8, image.stride(0),
+                                                      None, None, N, hw, ptr(img_feat), None, None, None, None, 2), "var_arm_encoder_fwd")
+                    c.check(c.lib.var_reward_dots_ids(c.handle, current_stream_handle(), ptr(img_feat), ptr(table.feat), table.rows + 1,
+                                                      ptr(self.goal_ids), ptr(self.current_ids) if cur else None, ptr(goal_feat),
+                                                      ptr(self.cur_feat) if cur else None, N, 3, ptr(self.dot),
+                                                      ptr(self.dot_img) if cur else None, ptr(self.dot_snd) if cur else None),
+                            "var_reward_dots_ids")
+                    return
                 if with_cur:                                     # the current sound is the forward's negative clip; no dot is armed
                     c.check(c.lib.var_arm_encoder_fwd(c.handle, current_stream_handle(), ptr(flat), ptr(image), is_u8, image.stride(0),
                                                       ptr(self.goal_sound) if with_goal else None, ptr(self.current_sound), N, hw,
@@ -260,6 +306,8 @@ class CollectStep:
                                               self.norm.slot.data_ptr() + 4, N), "var_rollout_move_at")
 
         bodies = {True: lambda: body(True), False: lambda: body(False), "reset": lambda: encoder(True, False)}
+        if table is not None:                                    # the ids are read on the device: one body serves every kind of step
+            bodies = {"step": lambda: body(True), "reset": lambda: encoder(True, False)}
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream())
         self._graphs = {}
@@ -281,12 +329,15 @@ class CollectStep:
         self._have_goal = False
         # pinned staging: image | extras | goal sound | current sound (sound-sound) | env_reward, done, bad -- each 16-byte aligned
         self._stage, off = {}, 0
-        sounds = [('goal_sound', self.goal_sound)] + ([('current_sound', self.current_sound)] if ss else [])
+        sounds = [] if table is not None else [('goal_sound', self.goal_sound)] + ([('current_sound', self.current_sound)] if ss else [])
         for name, t in [('image', image)] + [(k, obs[k]) for k in self._extra] + sounds + [('small', self._small)]:
             self._stage[name] = (off, t)
             off += (t.numel() * t.element_size() + 15) // 16 * 16
         self._pin = torch.empty(off, dtype=torch.uint8).pin_memory()
         self._pin_np = self._pin.numpy()
+        if table is not None:                                    # (the one copy moves the whole block: no stray ids from fresh memory)
+            ids_np = self._pin_view('small')[1][8 * N:16 * N].view(np.int32)
+            ids_np[:N], ids_np[N:] = -1, table.silent
         self._event = torch.cuda.Event()
         self._event_live = False
 
@@ -345,8 +396,8 @@ class CollectStep:
         if self._event_live:
             self._event.synchronize()                            # the previous step's copies out of the block are done
         small = [(name, plan) for name, plan, _ in plans if name in small_names]
-        packed = bool(small) and all(plan is not None and plan[0] == 'host' for _, plan in small)
-        offs = {'env_reward': 0, 'done': 8 * self.num_envs, 'bad': 9 * self.num_envs}
+        packed = len(small) == self._n_small and all(plan is not None and plan[0] == 'host' for _, plan in small)
+        offs = self._small_offs
         for name, plan, buf in plans:
             if plan is None or plan[0] != 'host':
                 continue
@@ -356,7 +407,7 @@ class CollectStep:
                 pin, host = pin[offs[name]:offs[name] + n], host[offs[name]:offs[name] + n]
             else:
                 pin, host = self._pin_view(name)
-            np_dtype = {torch.uint8: np.uint8, torch.float32: np.float32, torch.float64: np.float64}[buf.dtype]
+            np_dtype = {torch.uint8: np.uint8, torch.float32: np.float32, torch.float64: np.float64, torch.int32: np.int32}[buf.dtype]
             np.copyto(host.view(np_dtype), plan[1].reshape(-1), casting='unsafe')
             if not (packed and name in small_names):
                 buf.view(-1).view(torch.uint8).copy_(pin, non_blocking=True)
@@ -369,17 +420,34 @@ class CollectStep:
         self._event_live = True
 
     # ---- the step ---------------------------------------------------------------------------------------------------------------
+    def _ids_value(self, ids, name, keep):
+        """One id argument with a clip table: an int32 device tensor as it is (a bad id there is the kernel's NaN rule), anything
+        else range-checked on the host -- before anything is staged."""
+        if torch.is_tensor(ids) and ids.is_cuda:
+            return ids
+        return self.clip_table.host_ids(ids, "CollectStep: " + name, self.num_envs, keep)
+
     @torch.no_grad()
-    def reset(self, image, extras, goal_sound):
+    def reset(self, image, extras, goal_sound=None, goal_ids=None):
         """envs.reset() + RL.py:137-141: embeds the first observation (the goal sound with it), writes the observations to
         the storage's slot 0, zeroes the discounted return, sets act_step.masks to 1 (the storage's masks[0]) and takes the
-        storage's step over as the device slot."""
+        storage's step over as the device slot.  Built with a clip table it takes goal_ids (N), every env's goal clip, instead
+        of goal_sound."""
         act, ro = self.act_step, self.rollouts
         self._check_ready(slot=False)
-        if goal_sound is None:
-            raise VarHipError("CollectStep.reset: the goal sound of the episode is required")
-        plans = self._plans(image, extras, goal_sound, [])
-        self._stage_inputs(plans)
+        if self.clip_table is not None:
+            if goal_ids is None or goal_sound is not None:
+                raise VarHipError("CollectStep.reset: built with a clip table -- the goal of every env comes as goal_ids")
+            goal_ids = self._ids_value(goal_ids, "goal_ids", False)
+            small = [('goal_ids', goal_ids, self.goal_ids)]
+            plans = self._plans(image, extras, None, small)
+            self._stage_inputs(plans, ('goal_ids',))
+            self._goal_set[:] = True
+        else:
+            if goal_sound is None:
+                raise VarHipError("CollectStep.reset: the goal sound of the episode is required")
+            plans = self._plans(image, extras, goal_sound, [])
+            self._stage_inputs(plans)
         self._graphs["reset"].replay()
         ro._move([ro._slot_seg(act.obs[k], ro.obs[k][0]) for k in ro.obs], None, self.num_envs)
         self.norm.reset()
@@ -389,13 +457,23 @@ class CollectStep:
         self._have_goal = True
 
     @torch.no_grad()
-    def observe(self, image, extras, env_reward, done, bad=None, goal_sound=None, current_sound=None):
+    def observe(self, image, extras, env_reward, done, bad=None, goal_sound=None, current_sound=None, goal_ids=None,
+                current_ids=None):
         """One env step: obs, reward, done, infos of envs.step -> the storage (RL.py:164-185).  env_reward (N) float64, done /
         bad (N) uint8 or bool (bad: 'bad_transition' in info; None = none).  current_sound: O['current_sound'], required when the
         reward has sound_sound (a step without it raises and changes nothing: storage, normaliser and device slot stay) and
         ignored otherwise.  Returns the (N,1) float32 reward buffer; nothing is read back from the device.  The next act is
-        act_step(act_step.obs, act_step.masks)."""
+        act_step(act_step.obs, act_step.masks).
+
+        Built with a clip table the sounds come as goal_ids / current_ids (N) instead: a goal id is a clip's row, table.silent,
+        or -1 = that env keeps its cached goal (None: every env does), so an env that starts an episode alone gets its new goal
+        alone; current_ids is required with sound_sound and ignored without.  Host ids are range-checked before anything is
+        staged (a bad id raises and changes nothing) and ride in the one small copy; int32 device tensors are not read back."""
         self._check_ready()
+        if self.clip_table is not None:
+            return self._observe_ids(image, extras, env_reward, done, bad, goal_sound, current_sound, goal_ids, current_ids)
+        if goal_ids is not None or current_ids is not None:
+            raise VarHipError("CollectStep.observe: clip ids need a CollectStep built with clip_table")
         if self.sound_sound and current_sound is None:
             raise VarHipError("CollectStep.observe: the reward has sound_sound on -- every step needs current_sound "
                               "(vec_pretext_normalize.py:82-95)")
@@ -411,6 +489,31 @@ class CollectStep:
         self._stage_inputs(plans, ('env_reward', 'done', 'bad'))
         self._graphs[goal_sound is not None].replay()
         self._have_goal = True
+        self._slot = self.rollouts.step = (self._slot + 1) % self.rollouts.num_steps
+        return self.norm.reward
+
+    def _observe_ids(self, image, extras, env_reward, done, bad, goal_sound, current_sound, goal_ids, current_ids):
+        self.clip_table.check(self.reward_model.model, self._flat)       # (_check_ready has just seen that the arena is self._flat)
+        if goal_sound is not None or current_sound is not None:
+            raise VarHipError("CollectStep.observe: built with a clip table -- the sounds come as goal_ids / current_ids")
+        if self.sound_sound and current_ids is None:
+            raise VarHipError("CollectStep.observe: the reward has sound_sound on -- every step needs current_ids "
+                              "(vec_pretext_normalize.py:82-95; clip_table.silent when nothing is heard)")
+        goal = self._keep_ids if goal_ids is None else self._ids_value(goal_ids, "goal_ids", True)
+        kept = np.zeros(self.num_envs, bool) if torch.is_tensor(goal) else goal == -1
+        if (kept & ~self._goal_set).any():
+            raise VarHipError("CollectStep.observe: no goal embedding is cached yet for envs "
+                              f"{np.nonzero(kept & ~self._goal_set)[0].tolist()} -- reset() or pass their goal ids")
+        if bad is None:
+            bad = self._zero_bad()
+        small = [('env_reward', env_reward, self.env_reward), ('goal_ids', goal, self.goal_ids)]
+        if self.sound_sound:
+            small.append(('current_ids', self._ids_value(current_ids, "current_ids", False), self.current_ids))
+        small += [('done', done, self.done), ('bad', bad, self.bad)]
+        plans = self._plans(image, extras, None, small)
+        self._stage_inputs(plans, tuple(name for name, _, _ in small))
+        self._graphs["step"].replay()
+        self._goal_set |= ~kept
         self._slot = self.rollouts.step = (self._slot + 1) % self.rollouts.num_steps
         return self.norm.reward
 

@@ -325,6 +325,43 @@ __global__ void __launch_bounds__(256) reward_dots_kernel(const float* __restric
     if (out_snd) out_snd[r] = t;
 }
 
+// reward_dots_kernel with the sound embeddings served from a device clip table (rows x dim) by per-row ids.  Goal id gid >= 0:
+// table[gid], which also becomes the row's goal_feat; gid == -1 (or no goal ids): goal_feat[r], the row's cached embedding.  With
+// current ids cur_feat[r] = table[cid] and out = s + t in reward_dots_kernel's grouping; without them out = s.  An id outside its
+// range (goal < -1 or >= table_rows, current < 0 or >= table_rows) leaves NaN in every output of the row and goal_feat[r] as it
+// was.  Loads are unconditional from clamped rows; the value is selected afterwards.
+__global__ void __launch_bounds__(256) reward_dots_ids_kernel(const float* __restrict__ a, const float* __restrict__ table, int table_rows,
+                                                              const int* __restrict__ goal_ids, const int* __restrict__ cur_ids,
+                                                              float* goal_feat, float* __restrict__ cur_feat, int rows, int dim,
+                                                              float* __restrict__ out, float* __restrict__ out_img,
+                                                              float* __restrict__ out_snd) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const int gid = goal_ids ? goal_ids[r] : -1, cid = cur_ids ? cur_ids[r] : 0;
+    const bool bad = gid < -1 || gid >= table_rows || cid < 0 || cid >= table_rows;
+    const bool fresh = gid >= 0 && !bad;
+    const float* tg = table + (size_t)(gid >= 0 && gid < table_rows ? gid : 0) * dim;
+    const float* tc = table + (size_t)(cid >= 0 && cid < table_rows ? cid : 0) * dim;
+    float* gr = goal_feat + (size_t)r * dim;
+    const float qnan = __int_as_float(0x7fc00000);
+    float s = 0.f, t = 0.f;
+    for (int k = 0; k < dim; ++k) {
+        const float fresh_v = tg[k], kept_v = gr[k];
+        const float g = fresh ? fresh_v : kept_v;
+        s += a[(size_t)r * dim + k] * g;
+        if (fresh) gr[k] = g;
+    }
+    if (cur_ids)
+        for (int k = 0; k < dim; ++k) {
+            const float cv = tc[k];
+            t += cv * gr[k];                                   // (this thread's own stores above, or the cached row)
+            cur_feat[(size_t)r * dim + k] = bad ? qnan : cv;
+        }
+    out[r] = bad ? qnan : (cur_ids ? s + t : s);
+    if (out_img) out_img[r] = bad ? qnan : s;
+    if (out_snd) out_snd[r] = bad ? qnan : t;
+}
+
 // inference-only forwards (save_for_bwd = 2) of at most kHead1MaxB images take the round-2 conv 1 + 2 head, at 84 x 84 and at most
 // kSmallMidB images also the small conv 3-5 kernels (img_conv_fwd.hip)
 static constexpr int kHead1MaxB = 64;
@@ -493,6 +530,21 @@ int var_reward_dots(var_ctx* c, void* stream, const float* image_feat, const flo
     SET_DEVICE(c);
     hipLaunchKernelGGL(reward_dots_kernel, dim3((rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, image_feat, goal_feat, cur_feat, rows,
                        dim, out, out_img, out_snd);
+    VAR_HIP_CHECK(c, hipGetLastError());
+    return VAR_OK;
+}
+
+int var_reward_dots_ids(var_ctx* c, void* stream, const float* image_feat, const float* table, int table_rows, const int* goal_ids,
+                        const int* cur_ids, float* goal_feat, float* cur_feat, int rows, int dim, float* out, float* out_img,
+                        float* out_snd) {
+    CHECK_CTX(c);
+    if (!image_feat || !table || table_rows < 1 || !goal_feat || (cur_ids && !cur_feat) || !out || rows < 1 || dim < 1 || dim > 64) {
+        VAR_SET_ERR(c, "var_reward_dots_ids: bad argument (rows %d, dim %d, table_rows %d)", rows, dim, table_rows);
+        return VAR_ERR_ARG;
+    }
+    SET_DEVICE(c);
+    hipLaunchKernelGGL(reward_dots_ids_kernel, dim3((rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, image_feat, table, table_rows,
+                       goal_ids, cur_ids, goal_feat, cur_feat, rows, dim, out, out_img, out_snd);
     VAR_HIP_CHECK(c, hipGetLastError());
     return VAR_OK;
 }

@@ -13,6 +13,10 @@
 //       current clips take the goal clips' sound branch -- with them in one pass of 2B clips while 2B <= kFusedClips (8 envs fill
 //       the fused GRU step's 16 columns: still one launch per time step), in a pass of their own otherwise -- and the tail's last
 //       workgroup also normalises their embedding and forms <image, goal> + <current, goal>.
+//   id step (var_ithor_reward_step_ids): the sounds' embeddings are rows of a device clip table that var_ithor_reward_embed
+//       filled once per checkpoint (passes of up to kFusedClips clips through the sound branch + one normalising launch each);
+//       the step is the image stack and ONE tail whose finishing thread gathers by per-row ids read on the device -- 7 launches
+//       on every kind of step, the goal cached per env.
 // The encoder is frozen: var_ithor_reward_pack copies the parameter arena into the plan's own memory and lays conv 2..6 out in
 // MFMA A-fragment order ONCE; every step reads that snapshot, so parameters loaded later change nothing until the next pack.
 // The plan owns every buffer it touches (nothing of var_ithor_plan / var_ithor_policy_plan / var_plan is borrowed), and no
@@ -99,14 +103,22 @@ __global__ void __launch_bounds__(256) rw_pack_kernel(const float* __restrict__ 
 // SS (RLRewardSoundSound, a step with current clips): the same thread also normalises the row's current-sound embedding from
 // cur_raw and forms calcReward's sum in reward_dots_kernel's grouping -- reward = <image, goal> + <current, goal>, two fp32 row
 // sums and one add; the two dots go out where asked for.  SS = false is the kernel as it always was.
+// IDS (var_ithor_reward_step_ids): the sound embeddings are rows of a device clip table, picked by per-row ids the finishing
+// thread reads itself -- nothing of a sound pass is waited for.  Goal id g >= 0: table[g], also written to goal_feat[row]; g == -1
+// (or no goal ids at all): goal_feat[row], the row's cached embedding.  With current ids cur_feat[row] = table[c] and the reward
+// is SS's sum; without them it is SS = false's.  A row with an id outside its range (goal < -1 or >= table_rows; current < 0 or
+// >= table_rows) gets NaN in image_feat, cur_feat and the rewards and keeps its goal_feat.  Every load is unconditional from a
+// clamped address, the value is selected afterwards.  IDS = false discards all of it: the two kernels above stay as they were.
 constexpr int kTailWG = kHidI;
-template <bool SS>
+template <bool SS, bool IDS = false>
 __global__ void __launch_bounds__(256) rw_tail_kernel(const float* __restrict__ a6, const float* __restrict__ w0, const float* __restrict__ b0,
                                                      const float* __restrict__ w1, const float* __restrict__ b1, int B, float* hid,
                                                      unsigned* ctr, const float* __restrict__ goal_raw, float* goal_feat,
                                                      float* __restrict__ image_feat, float* __restrict__ reward,
                                                      const float* __restrict__ cur_raw, float* __restrict__ cur_feat,
-                                                     float* __restrict__ reward_img, float* __restrict__ reward_snd) {
+                                                     float* __restrict__ reward_img, float* __restrict__ reward_snd,
+                                                     const float* __restrict__ table = nullptr, int table_rows = 0,
+                                                     const int* __restrict__ goal_ids = nullptr, const int* __restrict__ cur_ids = nullptr) {
     constexpr int N4 = kIRaw / 4, PER = (N4 + 63) / 64;       // 288 16-byte pieces of a row, 5 per lane (the last one half a wave)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = blockIdx.x;
     float4 w[PER];
@@ -166,6 +178,29 @@ __global__ void __launch_bounds__(256) rw_tail_kernel(const float* __restrict__ 
     const float a = s0 + b1[0], b = s1 + b1[1], c = s2 + b1[2];
     const float nrm = fmaxf(sqrtf(a * a + b * b + c * c), 1e-12f);
     const float y0 = a / nrm, y1 = b / nrm, y2 = c / nrm;
+    if constexpr (IDS) {
+        const int gid = goal_ids ? goal_ids[row] : -1, cid = cur_ids ? cur_ids[row] : 0;
+        const bool bad = gid < -1 || gid >= table_rows || cid < 0 || cid >= table_rows;
+        const bool fresh = gid >= 0 && !bad;                   // a new goal: the table's row, and it becomes the cached one
+        const float* tg = table + 3 * (gid >= 0 && gid < table_rows ? gid : 0);
+        const float* tc = table + 3 * (cid >= 0 && cid < table_rows ? cid : 0);
+        const float n0 = tg[0], n1 = tg[1], n2 = tg[2], k0 = goal_feat[3 * row], k1 = goal_feat[3 * row + 1], k2 = goal_feat[3 * row + 2];
+        const float c0 = tc[0], c1 = tc[1], c2 = tc[2];
+        const float g0 = fresh ? n0 : k0, g1 = fresh ? n1 : k1, g2 = fresh ? n2 : k2;
+        const float qnan = __int_as_float(0x7fc00000);
+        if (fresh) { goal_feat[3 * row] = g0; goal_feat[3 * row + 1] = g1; goal_feat[3 * row + 2] = g2; }
+        image_feat[3 * row] = bad ? qnan : y0; image_feat[3 * row + 1] = bad ? qnan : y1; image_feat[3 * row + 2] = bad ? qnan : y2;
+        float sd = 0.f;
+        sd += y0 * g0; sd += y1 * g1; sd += y2 * g2;
+        if (!cur_ids) { reward[row] = bad ? qnan : sd; return; }
+        cur_feat[3 * row] = bad ? qnan : c0; cur_feat[3 * row + 1] = bad ? qnan : c1; cur_feat[3 * row + 2] = bad ? qnan : c2;
+        float ss = 0.f;
+        ss += c0 * g0; ss += c1 * g1; ss += c2 * g2;
+        reward[row] = bad ? qnan : sd + ss;
+        if (reward_img) reward_img[row] = bad ? qnan : sd;
+        if (reward_snd) reward_snd[row] = bad ? qnan : ss;
+        return;
+    }
     float g0, g1, g2;
     if (goal_raw) {
         const float u = goal_raw[3 * row], v = goal_raw[3 * row + 1], t = goal_raw[3 * row + 2];
@@ -279,6 +314,15 @@ __global__ void rw_gru_gate_kernel(const float* __restrict__ GI, const float* __
     hnext[(long)clip * kSRaw + dir * kGh + j] = (1.f - z) * n + z * hp;
 }
 
+// var_ithor_reward_embed: F.normalize of a pass's head outputs, the tail's expression (x / max(|x|, 1e-12)), a thread per clip
+__global__ void __launch_bounds__(64) rw_embed_finish_kernel(const float* __restrict__ raw, float* __restrict__ out, int n) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const float u = raw[3 * i], v = raw[3 * i + 1], t = raw[3 * i + 2];
+    const float gn = fmaxf(sqrtf(u * u + v * v + t * t), 1e-12f);
+    out[3 * i] = u / gn; out[3 * i + 1] = v / gn; out[3 * i + 2] = t / gn;
+}
+
 // the fp32 gather-GEMM, whatever var_ithor_set_bf16 says
 template <class G, bool SEQ>
 int snd_conv(var_ctx* c, hipStream_t s, const ConvDims& d, const float* x, const float* w, const float* bias, float* y) {
@@ -347,6 +391,21 @@ int goal_branch(var_ctx* c, hipStream_t s, rew_state* st, const float* clips, co
     RUN(linear(c, s, sraw, P + L.sh_w0, P + L.sh_b0, st->hs1, B, kSRaw, 128, 1));
     RUN(linear(c, s, st->hs1, P + L.sh_w1, P + L.sh_b1, st->hs2, B, 128, 64, 1));
     RUN(linear(c, s, st->hs2, P + L.sh_w2, P + L.sh_b2, out, B, 64, 3, 0));
+    return VAR_OK;
+}
+
+// the image stack of every step, six launches: image -> a6 (B, 1152), what the tail reads
+int image_convs(var_ctx* c, hipStream_t s, rew_state* st, const void* image, int image_is_u8, long image_bstride, int B) {
+    const RewLayout& L = st->L;
+    const float* P = st->frozen;
+    const c3f::PackDesc& d = st->pack;
+    // conv 1: c1f_pack_kernel's convolution workgroups alone (the filters were packed once)
+    RUN(conv1(c, s, image, image_is_u8, image_bstride, P, L.iw[0], L.ib[0], st->a1, B, nullptr, c3f::PackDesc{}));
+    RUN(c3f::launch<IthorC2>(c, s, st->a1, st->wpk + d.wp_off[0], P + L.ib[1], st->p[1], B));
+    RUN(c3f::launch<IthorC3>(c, s, st->p[1], st->wpk + d.wp_off[1], P + L.ib[2], st->p[2], B));
+    RUN(c3f::launch<IthorC4>(c, s, st->p[2], st->wpk + d.wp_off[2], P + L.ib[3], st->p[3], B));
+    RUN(c3f::launch<IthorC5>(c, s, st->p[3], st->wpk + d.wp_off[3], P + L.ib[4], st->p[4], B));
+    RUN(c3f::launch_small<IthorC6>(c, s, st->p[4], st->wpk + d.wp_off[4], P + L.ib[5], st->a6, B));
     return VAR_OK;
 }
 }  // namespace
@@ -497,14 +556,7 @@ int var_ithor_reward_step_ex(var_ctx* c, void* stream, const float* params, cons
     hipStream_t s = (hipStream_t)stream;
     const RewLayout& L = st->L;
     const float* P = st->frozen;
-    const c3f::PackDesc& d = st->pack;
-    // conv 1: c1f_pack_kernel's convolution workgroups alone (the filters were packed once)
-    RUN(conv1(c, s, image, image_is_u8, image_bstride, P, L.iw[0], L.ib[0], st->a1, B, nullptr, c3f::PackDesc{}));
-    RUN(c3f::launch<IthorC2>(c, s, st->a1, st->wpk + d.wp_off[0], P + L.ib[1], st->p[1], B));
-    RUN(c3f::launch<IthorC3>(c, s, st->p[1], st->wpk + d.wp_off[1], P + L.ib[2], st->p[2], B));
-    RUN(c3f::launch<IthorC4>(c, s, st->p[2], st->wpk + d.wp_off[2], P + L.ib[3], st->p[3], B));
-    RUN(c3f::launch<IthorC5>(c, s, st->p[3], st->wpk + d.wp_off[3], P + L.ib[4], st->p[4], B));
-    RUN(c3f::launch_small<IthorC6>(c, s, st->p[4], st->wpk + d.wp_off[4], P + L.ib[5], st->a6, B));
+    RUN(image_convs(c, s, st, image, image_is_u8, image_bstride, B));
     const float* craw = nullptr;
     if (merged) {
         RUN(goal_branch(c, s, st, goal_mfcc, cur_mfcc, B, st->graw));
@@ -521,6 +573,64 @@ int var_ithor_reward_step_ex(var_ctx* c, void* stream, const float* params, cons
         hipLaunchKernelGGL(rw_tail_kernel<false>, dim3(kTailWG), dim3(256), 0, s, (const float*)st->a6, P + L.ih_w0, P + L.ih_b0, P + L.ih_w1,
                            P + L.ih_b1, B, st->hid, st->ctr, graw, goal_feat, image_feat, reward, (const float*)nullptr, (float*)nullptr,
                            (float*)nullptr, (float*)nullptr);
+    AC_CHECK(c);
+    return VAR_OK;
+}
+
+int var_ithor_reward_embed(var_ctx* c, void* stream, const float* params, const float* mfcc, int n, float* out) {
+    if (!c) return VAR_ERR_ARG;
+    rew_state* st = rew(c);
+    if (!st) { VAR_SET_ERR(c, "var_ithor_reward_embed: var_ithor_reward_plan first"); return VAR_ERR_PLAN; }
+    if (!params || !mfcc || !out || n < 1) { VAR_SET_ERR(c, "var_ithor_reward_embed: NULL argument or n < 1"); return VAR_ERR_ARG; }
+    if (!st->packed) { VAR_SET_ERR(c, "var_ithor_reward_embed: var_ithor_reward_pack first"); return VAR_ERR_STATE; }
+    if (params != st->packed_from) {
+        VAR_SET_ERR(c, "var_ithor_reward_embed: params is not the arena of the last var_ithor_reward_pack (pack again)");
+        return VAR_ERR_STATE;
+    }
+    VAR_HIP_CHECK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    // passes over the plan's own sound buffers, each on the fused GRU route: a clip never mixes with the others of its pass
+    const int pass = st->maxB < kFusedClips ? st->maxB : kFusedClips;
+    for (int at = 0; at < n; at += pass) {
+        const int m = n - at < pass ? n - at : pass;
+        RUN(goal_branch(c, s, st, mfcc + (size_t)at * kT * kF, nullptr, m, st->graw));
+        hipLaunchKernelGGL(rw_embed_finish_kernel, dim3(1), dim3(64), 0, s, (const float*)st->graw, out + (size_t)3 * at, m);
+        AC_CHECK(c);
+    }
+    return VAR_OK;
+}
+
+int var_ithor_reward_step_ids(var_ctx* c, void* stream, const float* params, const void* image, int image_is_u8, long image_bstride,
+                              const float* table, int table_rows, const int* goal_ids, const int* cur_ids, int B, float* image_feat,
+                              float* goal_feat, float* cur_feat, float* reward, float* reward_img, float* reward_snd) {
+    if (!c) return VAR_ERR_ARG;
+    rew_state* st = rew(c);
+    if (!st || B > st->maxB) { VAR_SET_ERR(c, "var_ithor_reward_step_ids: var_ithor_reward_plan(%d, 96) first", B); return VAR_ERR_PLAN; }
+    if (!params || !image || !image_feat || !goal_feat || !reward || B < 1 || (cur_ids && !cur_feat)) {
+        VAR_SET_ERR(c, "var_ithor_reward_step_ids: NULL argument or B < 1");
+        return VAR_ERR_ARG;
+    }
+    if (!table || table_rows < 1) {
+        VAR_SET_ERR(c, "var_ithor_reward_step_ids: no clip table (table_rows %d)", table_rows);
+        return VAR_ERR_ARG;
+    }
+    if (image_bstride < 3L * 96 * 96) {
+        VAR_SET_ERR(c, "var_ithor_reward_step_ids: image stride %ld < 3*96*96", image_bstride);
+        return VAR_ERR_ARG;
+    }
+    if (!st->packed) { VAR_SET_ERR(c, "var_ithor_reward_step_ids: var_ithor_reward_pack first"); return VAR_ERR_STATE; }
+    if (params != st->packed_from) {
+        VAR_SET_ERR(c, "var_ithor_reward_step_ids: params is not the arena of the last var_ithor_reward_pack (pack again)");
+        return VAR_ERR_STATE;
+    }
+    VAR_HIP_CHECK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const RewLayout& L = st->L;
+    const float* P = st->frozen;
+    RUN(image_convs(c, s, st, image, image_is_u8, image_bstride, B));
+    hipLaunchKernelGGL((rw_tail_kernel<false, true>), dim3(kTailWG), dim3(256), 0, s, (const float*)st->a6, P + L.ih_w0, P + L.ih_b0,
+                       P + L.ih_w1, P + L.ih_b1, B, st->hid, st->ctr, (const float*)nullptr, goal_feat, image_feat, reward,
+                       (const float*)nullptr, cur_feat, reward_img, reward_snd, table, table_rows, goal_ids, cur_ids);
     AC_CHECK(c);
     return VAR_OK;
 }

@@ -7,7 +7,8 @@ normalisation with clipping) and Envs/vec_env/running_mean_std.py:4-35 (streamin
 forward is the HIP path (VARPretextNet.forward); the rest is host arithmetic on (num_envs,) arrays in float64,
 as in the reference.  IntrinsicReward(model, sound_sound=True) is config.RLRewardSoundSound: the current sound of every step
 is embedded too and <current_sound_feat, goal_sound_feat> joins the reward, on the eager pair embeddings() / reward() and on the
-captured step().
+captured step().  build_clip_table() embeds a pool of clips once per checkpoint (ClipTable); capture(batch, clip_table=table)
+then takes clip indices instead of feature arrays (step_ids): no sound branch on the step, the goal cached per env.
 """
 import numpy as np
 import torch
@@ -55,6 +56,56 @@ class ReturnNormalizer:
         self.ret[:] = 0.0
 
 
+def _arena_key(flat, params):
+    """What a frozen model's arena is recognised by, besides the flat tensor itself: torch's version counters of it and of the
+    parameters (load_state_dict, in-place ops; edits through .data bump nothing -- build the table again after those)."""
+    return flat.data_ptr(), flat._version, sum([p._version for p in params])
+
+
+class ClipTable:
+    """The embeddings of a pool of sound clips under one frozen checkpoint (IntrinsicReward.build_clip_table): the env's
+    sounds come from a finite, unaugmented pool (Envs/audioLoader.py:166-237) and the encoder does not change, so a clip's
+    embedding is a constant and a reward step only needs the clip's index.
+
+    feat: (rows + 1, dim) f32 on the device; row i is clip i, row `silent` (== rows) the embedding of the all-zero feature
+    matrix the envs send when nothing is heard.  The table remembers the arena it was built from: used with a model whose
+    arena has moved or changed since, it raises VarHipError -- build the table again (the pack-once rule's discipline)."""
+
+    def __init__(self, feat, model):
+        self.feat = feat
+        self.rows = int(feat.shape[0]) - 1
+        self.silent = self.rows
+        self.dim = int(feat.shape[1])
+        self._model = model
+        self._flat = model.flat_parameters()
+        self._params = list(model.parameters())                  # (the Parameter objects outlive load_state_dict and .to())
+        self._key = _arena_key(self._flat, self._params)
+
+    def check(self, model, flat=None):
+        """Raises unless `model` still has the arena the table was built from; flat: model.flat_parameters() where the caller
+        has just taken it (the walk over the modules is most of this check's cost on the step path)."""
+        from ._lib import VarHipError
+        flat = model.flat_parameters() if flat is None else flat
+        if model is not self._model or flat is not self._flat or _arena_key(flat, self._params) != self._key:
+            raise VarHipError("ClipTable: the encoder's parameter arena has moved or changed since the table was built "
+                              "(load_state_dict, .to(), another model): build the table again")
+
+    def host_ids(self, ids, name, batch, keep=False):
+        """Host ids as a checked (batch,) int32 array; keep: -1 ("the cached goal of that env") is allowed.  A bad id raises."""
+        from ._lib import VarHipError
+        a = np.asarray(ids.numpy() if torch.is_tensor(ids) else ids)
+        if a.shape != (batch,) or a.dtype.kind not in "iu":
+            raise VarHipError(f"{name}: {batch} integer clip ids expected, got shape {a.shape} of {a.dtype}")
+        lo = -1 if keep else 0
+        if a.size and (a.min() < lo or a.max() > self.rows):
+            raise VarHipError(f"{name}: ids outside {lo}..{self.rows} (rows 0..{self.rows - 1} are the clips, {self.rows} is "
+                              f"silence{', -1 keeps the cached goal' if keep else ''}): {a.tolist()}")
+        return a.astype(np.int32)
+
+
+CLIP_CHUNK = 256        # clips embedded per call of build_clip_table: at most 25 MB (Kuka: 4) of features beside the table
+
+
 class IntrinsicReward:
     """reward = env_reward + <image_feat, goal_sound_feat> (+ <current_sound_feat, goal_sound_feat> when
     sound_sound is on): getEmbeddings + calcReward of the reference wrapper, on the frozen HIP encoder.
@@ -85,8 +136,190 @@ class IntrinsicReward:
         cur_feat = d["sound_feat_negative"].cpu().numpy() if (self.sound_sound and current_sound is not None) else 0.0
         return image_feat, goal_feat, cur_feat
 
+    # ---- the clip table: every pool clip's embedding, once per checkpoint -------------------------------------
+    @torch.no_grad()
+    def build_clip_table(self, features=None, pcm=None, lens=None, chunk=CLIP_CHUNK):
+        """Embed a pool of sound clips once -> ClipTable.  Either `features`, (rows,) + sound_dim precomputed feature matrices,
+        or `pcm`, int16 (rows, stride) samples with `lens` (rows) -- a TripletPool's clips / clip_len as they are; PCM runs
+        through ops.mfcc (Kuka: 100 frames) or ops.mfcc_psf (iTHOR: 600 frames) on the device.  Host arrays and device tensors
+        are both taken; the work goes in chunks of `chunk` clips so that only a chunk's features exist at once.  The iTHOR
+        encoder is var_ithor_reward_embed (the weights are packed here); the Kuka encoder var_arm_encoder_fwd with the clips as
+        mfcc_pos alone, save_for_bwd = 2.  A row's bits do not depend on `chunk` or on its neighbours."""
+        from ._lib import Context, VarHipError, current_stream_handle, ptr
+        from .ithor import IthorVARPretextNet
+        from . import ops
+        m = self.model
+        flat = m.flat_parameters()
+        if not flat.is_cuda:
+            raise VarHipError("IntrinsicReward.build_clip_table needs the model on the GPU (no CPU fallback)")
+        if (features is None) == (pcm is None):
+            raise VarHipError("IntrinsicReward.build_clip_table: features or pcm (with lens), one of the two")
+        dev = flat.device
+        sound_dim = tuple(m.config.sound_dim)
+        src = features if pcm is None else pcm
+        src = src if torch.is_tensor(src) else torch.from_numpy(np.ascontiguousarray(src))
+        rows, chunk = int(src.shape[0]), int(chunk)
+        if rows < 1 or chunk < 1:
+            raise VarHipError("IntrinsicReward.build_clip_table: at least one clip and chunk >= 1")
+        if pcm is None and (tuple(src.shape[1:]) != sound_dim or src.dtype != torch.float32):
+            raise VarHipError(f"IntrinsicReward.build_clip_table: features are {src.dtype} {tuple(src.shape)}, expected float32 "
+                              f"(rows,) + {sound_dim}")
+        if pcm is not None:
+            if src.dtype != torch.int16 or src.dim() != 2:
+                raise VarHipError("IntrinsicReward.build_clip_table: pcm must be int16 (rows, stride)")
+            if lens is None:
+                lens = np.full(rows, src.shape[1], np.int32)
+            lens = (lens if torch.is_tensor(lens) else torch.from_numpy(np.ascontiguousarray(lens))).to(torch.int32)
+            if tuple(lens.shape) != (rows,):
+                raise VarHipError(f"IntrinsicReward.build_clip_table: lens has shape {tuple(lens.shape)}, expected ({rows},)")
+        ithor = isinstance(m, IthorVARPretextNet)
+        c = Context.get(dev.index)
+        if ithor:
+            if flat.numel() != c.lib.var_ithor_param_count():
+                raise VarHipError("parameter arena does not match var_ithor_param_count()")
+            c.check(c.lib.var_ithor_reward_plan(c.handle, 16, int(m.config.img_dim[1])), "var_ithor_reward_plan")
+            c.check(c.lib.var_ithor_reward_pack(c.handle, current_stream_handle(), ptr(flat)), "var_ithor_reward_pack")
+        else:
+            c.ensure_plan(min(chunk, rows + 1), int(m.config.img_dim[1]))
+            w = m.hip_weights(c, force=True)
+        feat = torch.empty((rows + 1, self.rep), dtype=torch.float32, device=dev)
+
+        def embed(x, out):
+            n = x.shape[0]
+            if ithor:
+                c.check(c.lib.var_ithor_reward_embed(c.handle, current_stream_handle(), ptr(flat), ptr(x), n, ptr(out)),
+                        "var_ithor_reward_embed")
+                return
+            w.bind()
+            c.check(c.lib.var_arm_encoder_fwd(c.handle, current_stream_handle(), ptr(flat), None, 0, 0, ptr(x), None, n,
+                                              int(m.config.img_dim[1]), None, ptr(out), None, None, None, 2), "var_arm_encoder_fwd")
+
+        for at in range(0, rows, chunk):
+            part = src[at:at + chunk].to(dev)
+            if pcm is not None:
+                front = ops.mfcc_psf if ithor else ops.mfcc
+                part = front(part, lens[at:at + chunk].to(dev), out_frames=sound_dim[1])
+            embed(part.contiguous(), feat[at:at + part.shape[0]])
+        embed(torch.zeros((1,) + sound_dim, dtype=torch.float32, device=dev), feat[rows:])          # nothing is heard
+        torch.cuda.current_stream().synchronize()                # (the chunks' features may be freed now)
+        return ClipTable(feat, m)
+
     # ---- latency path: the whole frozen-encoder step as a replayed HIP graph --------------------------------
-    def capture(self, batch):
+    def _capture_ids(self, batch, table):
+        """capture(batch, clip_table=table): ONE graph over static id buffers -- the image stack and one gather-and-dot launch
+        (iTHOR: var_ithor_reward_step_ids, 7 kernels; Kuka: an image-only var_arm_encoder_fwd + var_reward_dots_ids)."""
+        from ._lib import Context, VarHipError, current_stream_handle, new_graph, ptr
+        from .ithor import IthorVARPretextNet
+        if not isinstance(table, ClipTable):
+            raise VarHipError("IntrinsicReward.capture: clip_table must be a ClipTable (build_clip_table)")
+        m = self.model
+        table.check(m)
+        flat = m.flat_parameters()
+        dev = flat.device
+        c = Context.get(dev.index)
+        hw = int(m.config.img_dim[1])
+        B = int(batch)
+        ss = bool(self.sound_sound)
+        ithor = isinstance(m, IthorVARPretextNet)
+        if table.dim != 3 or table.feat.device != dev:
+            raise VarHipError("IntrinsicReward.capture: the clip table is not this model's (dimension or device)")
+        if ithor:
+            c.check(c.lib.var_ithor_reward_plan(c.handle, B, hw), "var_ithor_reward_plan")
+            c.check(c.lib.var_ithor_reward_pack(c.handle, current_stream_handle(), ptr(flat)), "var_ithor_reward_pack")
+        else:
+            c.ensure_plan(B, hw)
+            w = m.hip_weights(c, force=True)
+        self._B, self._table, self._ithor = B, table, ithor
+        self._img = torch.zeros((B,) + tuple(m.config.img_dim), dtype=torch.uint8, device=dev)
+        self._image_feat = torch.zeros((B, 3), device=dev)
+        self._goal_feat = torch.zeros((B, 3), device=dev)
+        self._reward = torch.zeros((B,), device=dev)
+        self._ids = torch.full((2, B), -1, dtype=torch.int32, device=dev)
+        self.goal_ids, self.current_ids = self._ids[0], self._ids[1]
+        self.current_ids.fill_(table.silent)
+        self._goal_set = np.zeros(B, bool)                       # per env: has a goal embedding been cached?
+        self.current_sound = None
+        if ss:
+            self.cur_feat = torch.zeros((B, 3), device=dev)
+            self.img_sound_dot = torch.zeros((B,), device=dev)
+            self.sound_sound_dot = torch.zeros((B,), device=dev)
+        cur = dict(ids=ptr(self.current_ids), feat=ptr(self.cur_feat), img=ptr(self.img_sound_dot),
+                   snd=ptr(self.sound_sound_dot)) if ss else dict(ids=None, feat=None, img=None, snd=None)
+
+        def body():
+            if ithor:
+                c.check(c.lib.var_ithor_reward_step_ids(c.handle, current_stream_handle(), ptr(flat), ptr(self._img), 1,
+                                                        self._img.stride(0), ptr(table.feat), table.rows + 1, ptr(self.goal_ids),
+                                                        cur["ids"], B, ptr(self._image_feat), ptr(self._goal_feat), cur["feat"],
+                                                        ptr(self._reward), cur["img"], cur["snd"]), "var_ithor_reward_step_ids")
+                return
+            w.bind()
+            c.check(c.lib.var_arm_encoder_fwd(c.handle, current_stream_handle(), ptr(flat), ptr(self._img), 1, self._img.stride(0),
+                                              None, None, B, hw, ptr(self._image_feat), None, None, None, None, 2),
+                    "var_arm_encoder_fwd")
+            c.check(c.lib.var_reward_dots_ids(c.handle, current_stream_handle(), ptr(self._image_feat), ptr(table.feat),
+                                              table.rows + 1, ptr(self.goal_ids), cur["ids"], ptr(self._goal_feat), cur["feat"], B, 3,
+                                              ptr(self._reward), cur["img"], cur["snd"]), "var_reward_dots_ids")
+
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            body()                                               # warm-up outside capture (lazy kernel attributes)
+            g = new_graph()
+            with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+                body()
+            self._graphs = {"ids": g}
+        torch.cuda.current_stream().wait_stream(side)
+        return self
+
+    def _ids_input(self, ids, name, keep):
+        """One id argument of step_ids: ('host', checked int32 array) or ('dev', int32 tensor); refuses everything else."""
+        from ._lib import VarHipError
+        if torch.is_tensor(ids) and ids.is_cuda:
+            if ids.dtype != torch.int32 or tuple(ids.shape) != (self._B,) or ids.device != self._ids.device:
+                raise VarHipError(f"IntrinsicReward.step_ids: {name} on the device must be int32 ({self._B},) on {self._ids.device}")
+            return 'dev', ids
+        return 'host', self._table.host_ids(ids, "IntrinsicReward.step_ids: " + name, self._B, keep)
+
+    def step_ids(self, image_u8, goal_ids=None, current_ids=None):
+        """One env step of a capture(batch, clip_table=table): clip indices instead of feature arrays.  goal_ids (B): a clip's
+        row, table.silent, or -1 = keep the goal cached for THAT env; None = -1 everywhere.  current_ids (B): the sound heard
+        in this step (table.silent when none); required with sound_sound, ignored without.  Host arrays are range-checked
+        before anything is copied -- a bad id raises and changes nothing; int32 device tensors are taken as they are and a bad
+        id there turns that env's outputs into NaN (include/var_hip.h).  A -1 for an env that never got a goal raises (ids on
+        the device are not read back: after such a step every env counts as having one).  Returns (image_feat, goal_feat,
+        reward) as step() does; cur_feat, img_sound_dot and sound_sound_dot are attributes when sound_sound is on."""
+        from ._lib import VarHipError
+        if "ids" not in getattr(self, "_graphs", {}):
+            raise VarHipError("IntrinsicReward.step_ids: capture(batch, clip_table=table) first")
+        self._table.check(self.model, self.model._flat)          # (.to() re-flattens at once: no walk over the modules per step)
+        ss = bool(self.sound_sound)
+        if ss and current_ids is None:
+            raise VarHipError("IntrinsicReward.step_ids: sound_sound is on -- every step needs current_ids "
+                              "(vec_pretext_normalize.py:82-95; table.silent when nothing is heard)")
+        goal = ('host', np.full(self._B, -1, np.int32)) if goal_ids is None else self._ids_input(goal_ids, "goal_ids", True)
+        ids = [goal] + ([self._ids_input(current_ids, "current_ids", False)] if ss else [])
+        kept = goal[1] == -1 if goal[0] == 'host' else np.zeros(self._B, bool)
+        if (kept & ~self._goal_set).any():
+            raise VarHipError("IntrinsicReward.step_ids: no goal embedding is cached yet for envs "
+                              f"{np.nonzero(kept & ~self._goal_set)[0].tolist()} -- pass their goal ids (pretext_base.py:26-32)")
+        image_u8 = torch.as_tensor(image_u8)
+        if tuple(image_u8.shape) != tuple(self._img.shape) or image_u8.dtype != torch.uint8:
+            raise VarHipError(f"IntrinsicReward.step_ids: image is {image_u8.dtype} {tuple(image_u8.shape)}, expected uint8 "
+                              f"{tuple(self._img.shape)}")
+        if self._ithor and not image_u8.is_cuda:
+            raise VarHipError("IntrinsicReward.step_ids: image must be a CUDA tensor (no CPU fallback)")
+        self._img.copy_(image_u8, non_blocking=True)
+        if all(kind == 'host' for kind, _ in ids):               # one copy for both
+            self._ids[:len(ids)].copy_(torch.from_numpy(np.stack([a for _, a in ids])), non_blocking=True)
+        else:
+            for buf, (kind, a) in zip(self._ids, ids):
+                buf.copy_(a if kind == 'dev' else torch.from_numpy(a), non_blocking=True)
+        self._goal_set |= ~kept
+        self._graphs["ids"].replay()
+        return self._image_feat, self._goal_feat, self._reward
+
+    def capture(self, batch, clip_table=None):
         """Capture the frozen encoder for a fixed number of envs (BASELINE config 5: 8) into two HIP graphs --
         image + goal sound (first step of an episode) and image only (later steps: the goal embedding is reused) --
         over static device buffers.  Weights are packed once here: call again after loading another checkpoint.
@@ -101,8 +334,13 @@ class IntrinsicReward:
         is calcReward's <image_feat, goal_feat> + <current_sound_feat, goal_feat> (var_reward_dots' grouping).  Further
         static buffers, as attributes: current_sound (B,) + sound_dim, cur_feat (B,3), img_sound_dot and sound_sound_dot
         (B,).  The Kuka encoder takes the current sound as var_arm_encoder_fwd's mfcc_neg and var_reward_dots follows the
-        forward (var_set_reward_dot is not armed); the iTHOR encoder is var_ithor_reward_step_ex."""
+        forward (var_set_reward_dot is not armed); the iTHOR encoder is var_ithor_reward_step_ex.
+
+        With clip_table (build_clip_table) the sounds arrive as clip indices: ONE graph, no sound branch in it, static int32
+        buffers goal_ids / current_ids (B,), and step_ids() instead of step().  Without it everything is as above."""
         from ._lib import Context, current_stream_handle, new_graph, ptr
+        if clip_table is not None:
+            return self._capture_ids(batch, clip_table)
         m = self.model
         from .ithor import IthorVARPretextNet
         self.current_sound = None                # (set by a capture with sound_sound)
