@@ -55,7 +55,7 @@ def main():
     snd_np[:, :, :, 0] += 18.0
     snd = torch.from_numpy(snd_np).cuda()
     c = Context.get(0)
-    have_new = hasattr(c.lib, "var_ithor_reward_step") and hasattr(var_amd.IntrinsicReward, "_capture_ithor")
+    have_new = hasattr(c.lib, "var_ithor_reward_step")
     legs, outs = {}, {}
 
     if a.replay_only != "new":

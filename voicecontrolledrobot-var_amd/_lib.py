@@ -1,5 +1,6 @@
 """ctypes binding of libvar_hip.so (include/var_hip.h).  Fails loudly when the library is
 missing or a call returns an error -- there is no fallback path."""
+import contextlib
 import ctypes
 import os
 import subprocess
@@ -225,24 +226,33 @@ class Context:
     def new_weights(self):
         return Weights(self)
 
-    def capture(self, groups):
-        """Capture each group of bodies (callables that enqueue C-ABI launches on the current stream) into one HIP
-        graph; returns one replay callable per group."""
+    @contextlib.contextmanager
+    def capturing(self):
+        """The package's one capture block: inside the `with`, the current stream is a side stream that waited for the caller's,
+        and the value is graph(body, warm=False) -> the HIP graph of `body`, a callable that enqueues C-ABI launches on the
+        current stream; warm: run it once first, outside the capture (lazy kernel attributes).  What the caller does besides
+        (undoing what a warm-up touched) runs on the side stream too; the caller's stream waits for it at the end."""
         import torch
         dev = torch.device("cuda", self.device_index)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
-        graphs = []
+
+        def graph(body, warm=False):
+            if warm:
+                body()
+            g = new_graph()
+            # thread-local capture: the RCCL watchdog thread of torch.distributed may query events meanwhile
+            with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+                body()
+            return g
         with torch.cuda.stream(side):
-            for bodies in groups:
-                g = new_graph()
-                # thread-local capture: the RCCL watchdog thread of torch.distributed may query events meanwhile
-                with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                    for body in bodies:
-                        body()
-                graphs.append(g)
+            yield graph
         torch.cuda.current_stream(dev).wait_stream(side)
-        return [g.replay for g in graphs]
+
+    def capture(self, groups):
+        """Capture each group of bodies into one HIP graph (capturing(), no warm-up); returns one replay callable per group."""
+        with self.capturing() as graph:
+            return [graph(lambda bodies=bodies: [body() for body in bodies]).replay for bodies in groups]
 
     def ensure_plan(self, batch, hw):
         if self.plan[1] != hw or self.plan[0] < batch:

@@ -283,17 +283,10 @@ class ActStep:
                                           ptr(self.action_log_probs), ptr(self._hout), ptr(self._hxs), hidden),
                     "var_policy_dist")
 
-        from ._lib import new_graph
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            body()                                               # warm-up outside capture (lazy kernel attributes)
-            self._graph = new_graph()
-            with torch.cuda.graph(self._graph, stream=side, capture_error_mode="thread_local"):
-                body()
+        with c.capturing() as graph:
+            self._graph = graph(body, warm=True)
             self._rng.copy_(self._rng0)                          # (the warm-up drew from step 0 and carried its state)
             self._hxs.zero_()
-        torch.cuda.current_stream().wait_stream(side)
 
     @property
     def rng_step(self):

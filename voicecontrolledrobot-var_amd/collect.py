@@ -14,15 +14,16 @@ RL.py:137-141, 171-185) -- as ONE replayed HIP graph over buffers the act step a
 
 DeviceReturnNormalizer is the normaliser alone (reward.ReturnNormalizer with its state on the device).  GPU only: there is no
 CPU fallback.  config.RLRewardSoundSound is IntrinsicReward(encoder, sound_sound=True): every observe() then takes the step's
-current sound as well, the same replay embeds it (var_ithor_reward_step_ex, or var_arm_encoder_fwd's negative clip +
-var_reward_dots) and the normaliser's dot is <image_feat, goal_feat> + <current_sound_feat, goal_feat>.  Not here: the act
+current sound as well, the same replay embeds it and the normaliser's dot is <image_feat, goal_feat> +
+<current_sound_feat, goal_feat>.  The encoder's launches, route by route, are reward_step.RewardStep's.  Not here: the act
 replay inside the same graph (the value and action of slot T would be stale after the update) and _obfilt (off in both
 reference configurations)."""
 import numpy as np
 import torch
 
-from ._lib import Context, MoveAtSeg, MoveSeg, VarHipError, current_stream_handle, new_graph, ptr
+from ._lib import Context, MoveAtSeg, MoveSeg, VarHipError, current_stream_handle, ptr
 from .reward import ReturnNormalizer
+from .reward_step import RewardStep
 
 MAX_ENVS = 64                                                    # the reward step's limit (var_ithor_reward_plan; save_for_bwd = 2)
 MAX_SEGS = 16                                                    # VAR_MOVE_MAX_SEGS
@@ -148,9 +149,8 @@ def insert_segments(act, rollouts, reward, bad_masks):
 
 class CollectStep:
     """One env step of the collection loop (RL.py:163-185 without the simulator) as one replay: the reward step of the frozen
-    encoder (var_arm_encoder_fwd + var_row_dot / var_set_reward_dot, or var_ithor_reward_step; with reward.sound_sound
-    var_arm_encoder_fwd + var_reward_dots, or var_ithor_reward_step_ex), var_reward_norm_step and one var_rollout_move_at,
-    captured twice -- with and without a new goal sound.  The act step's own buffers are the operands:
+    encoder (reward_step.RewardStep.launch: the entries of each route are listed there), var_reward_norm_step and one
+    var_rollout_move_at, captured twice -- with and without a new goal sound.  The act step's own buffers are the operands:
     act_step.obs['image'] is the encoder's input, obs['image_feat'] / obs['goal_sound_feat'] its outputs (the cached goal
     embedding of the later steps lives there), act_step.masks the normaliser's mask output; nothing is copied between the parts.
 
@@ -170,15 +170,13 @@ class CollectStep:
 
     clip_table (IntrinsicReward.build_clip_table of the same encoder): the sounds arrive as clip indices, not feature arrays --
     reset(image, extras, goal_ids=...), observe(..., goal_ids=None, current_ids=None); a goal id of -1 keeps THAT env's cached
-    goal, so an env that starts an episode alone gets its new goal alone.  The replay holds no sound branch (iTHOR:
-    var_ithor_reward_step_ids, 7 kernels; Kuka: an image-only var_arm_encoder_fwd + var_reward_dots_ids) and is captured once --
-    the ids are read on the device -- beside the reset's; host ids ride in the small pinned block (2 * 4N bytes more, still
+    goal, so an env that starts an episode alone gets its new goal alone.  The replay holds no sound branch and is captured once
+    -- the ids are read on the device -- beside the reset's; host ids ride in the small pinned block (2 * 4N bytes more, still
     one copy) and are range-checked before anything is staged; self.goal_ids / self.current_ids are the device buffers.
     Without clip_table everything is as described above."""
 
     def __init__(self, reward, act_step, rollouts, gamma=0.99, cliprew=10., epsilon=1e-8, normalize=True, clip_table=None):
         from .actor_critic import ActStep
-        from .ithor import IthorVARPretextNet
         from .reward import ClipTable, IntrinsicReward
         from .rollout import RolloutStorage
         if not isinstance(reward, IntrinsicReward) or not isinstance(act_step, ActStep) or not isinstance(rollouts, RolloutStorage):
@@ -210,7 +208,6 @@ class CollectStep:
         if table is not None:
             if not isinstance(table, ClipTable) or table.dim != 3 or table.feat.device != dev:
                 raise VarHipError("CollectStep: clip_table must be a ClipTable of this encoder (IntrinsicReward.build_clip_table)")
-            table.check(m)
         else:
             self.goal_sound = torch.zeros((N,) + tuple(m.config.sound_dim), dtype=torch.float32, device=dev)
         self.dot = torch.zeros(N, device=dev)
@@ -234,97 +231,34 @@ class CollectStep:
             self._small_offs.update(goal_ids=8 * N, current_ids=12 * N)
             self.goal_ids.fill_(-1)
             self.current_ids.fill_(table.silent)
-            self._goal_set = np.zeros(N, bool)                   # per env: has a goal embedding been cached?
             self._keep_ids = np.full(N, -1, np.int32)
         image, img_feat, goal_feat = obs['image'], obs['image_feat'], obs['goal_sound_feat']
-        is_u8 = int(image.dtype == torch.uint8)
-        ithor = isinstance(m, IthorVARPretextNet)
-        hw = int(m.config.img_dim[1])
-        if ithor:
-            if flat.numel() != c.lib.var_ithor_param_count():
-                raise VarHipError("parameter arena does not match var_ithor_param_count()")
-            c.check(c.lib.var_ithor_reward_plan_ex(c.handle, N, hw, int(ss)), "var_ithor_reward_plan_ex")
-            c.check(c.lib.var_ithor_reward_pack(c.handle, current_stream_handle(), ptr(flat)), "var_ithor_reward_pack")
-
-            def encoder(with_goal, with_cur=ss):
-                if table is not None:                            # 7 kernels, whatever the ids say
-                    cur = with_cur and ss
-                    c.check(c.lib.var_ithor_reward_step_ids(c.handle, current_stream_handle(), ptr(flat), ptr(image), is_u8,
-                                                            image.stride(0), ptr(table.feat), table.rows + 1, ptr(self.goal_ids),
-                                                            ptr(self.current_ids) if cur else None, N, ptr(img_feat), ptr(goal_feat),
-                                                            ptr(self.cur_feat) if cur else None, ptr(self.dot),
-                                                            ptr(self.dot_img) if cur else None, ptr(self.dot_snd) if cur else None),
-                            "var_ithor_reward_step_ids")
-                    return
-                if with_cur:
-                    c.check(c.lib.var_ithor_reward_step_ex(c.handle, current_stream_handle(), ptr(flat), ptr(image), is_u8,
-                                                           image.stride(0), ptr(self.goal_sound) if with_goal else None,
-                                                           ptr(self.current_sound), N, ptr(img_feat), ptr(goal_feat), ptr(self.cur_feat),
-                                                           ptr(self.dot), ptr(self.dot_img), ptr(self.dot_snd)), "var_ithor_reward_step_ex")
-                    return
-                c.check(c.lib.var_ithor_reward_step(c.handle, current_stream_handle(), ptr(flat), ptr(image), is_u8, image.stride(0),
-                                                    ptr(self.goal_sound) if with_goal else None, N, ptr(img_feat), ptr(goal_feat),
-                                                    ptr(self.dot)), "var_ithor_reward_step")
-        else:
-            c.ensure_plan(N, hw)
-            w = m.hip_weights(c, force=True)                     # the frozen model's own packed image; the graphs keep its address
-
-            def encoder(with_goal, with_cur=ss):
-                w.bind()
-                if table is not None:                            # image only; the sounds' embeddings are gathered by the dots' launch
-                    cur = with_cur and ss
-                    c.check(c.lib.var_arm_encoder_fwd(c.handle, current_stream_handle(), ptr(flat), ptr(image), is_u8, image.stride(0),
-                                                      None, None, N, hw, ptr(img_feat), None, None, None, None, 2), "var_arm_encoder_fwd")
-                    c.check(c.lib.var_reward_dots_ids(c.handle, current_stream_handle(), ptr(img_feat), ptr(table.feat), table.rows + 1,
-                                                      ptr(self.goal_ids), ptr(self.current_ids) if cur else None, ptr(goal_feat),
-                                                      ptr(self.cur_feat) if cur else None, N, 3, ptr(self.dot),
-                                                      ptr(self.dot_img) if cur else None, ptr(self.dot_snd) if cur else None),
-                            "var_reward_dots_ids")
-                    return
-                if with_cur:                                     # the current sound is the forward's negative clip; no dot is armed
-                    c.check(c.lib.var_arm_encoder_fwd(c.handle, current_stream_handle(), ptr(flat), ptr(image), is_u8, image.stride(0),
-                                                      ptr(self.goal_sound) if with_goal else None, ptr(self.current_sound), N, hw,
-                                                      ptr(img_feat), ptr(goal_feat) if with_goal else None, ptr(self.cur_feat), None, None,
-                                                      2), "var_arm_encoder_fwd")
-                    c.check(c.lib.var_reward_dots(c.handle, current_stream_handle(), ptr(img_feat), ptr(goal_feat), ptr(self.cur_feat), N,
-                                                  3, ptr(self.dot), ptr(self.dot_img), ptr(self.dot_snd)), "var_reward_dots")
-                    return
-                if not with_goal:                                # the forward itself leaves <image_feat, goal_feat>
-                    c.check(c.lib.var_set_reward_dot(c.handle, ptr(goal_feat), ptr(self.dot)), "var_set_reward_dot")
-                c.check(c.lib.var_arm_encoder_fwd(c.handle, current_stream_handle(), ptr(flat), ptr(image), is_u8, image.stride(0),
-                                                  ptr(self.goal_sound) if with_goal else None, None, N, hw, ptr(img_feat),
-                                                  ptr(goal_feat) if with_goal else None, None, None, None, 2), "var_arm_encoder_fwd")
-                if with_goal:
-                    c.check(c.lib.var_row_dot(c.handle, current_stream_handle(), ptr(img_feat), ptr(goal_feat), N, 3, ptr(self.dot)),
-                            "var_row_dot")
-        self._flat = flat
+        more = dict(cur_feat=self.cur_feat, reward_img=self.dot_img, reward_snd=self.dot_snd) if ss else {}
+        goal, cur = (self.goal_sound, self.current_sound if ss else None) if table is None else (self.goal_ids, self.current_ids)
+        rs = self._reward_step = RewardStep(c, m, N, image=image, is_u8=image.dtype == torch.uint8, goal=goal, cur=cur,
+                                            image_feat=img_feat, goal_feat=goal_feat, reward=self.dot, sound_sound=ss,
+                                            clip_table=table, **more)
+        self._flat = rs.flat
 
         def body(with_goal):
-            encoder(with_goal)
+            rs.launch(with_goal, True)
             self.norm._launch(self.dot, self.env_reward, self.done, self.bad, act_step.masks)
             c.check(c.lib.var_rollout_move_at(c.handle, current_stream_handle(), self._segs, len(self._segs),
                                               self.norm.slot.data_ptr() + 4, N), "var_rollout_move_at")
 
-        bodies = {True: lambda: body(True), False: lambda: body(False), "reset": lambda: encoder(True, False)}
+        bodies = {True: lambda: body(True), False: lambda: body(False), "reset": lambda: rs.launch(True, False)}
         if table is not None:                                    # the ids are read on the device: one body serves every kind of step
-            bodies = {"step": lambda: body(True), "reset": lambda: encoder(True, False)}
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
+            bodies = {"step": lambda: body(True), "reset": lambda: rs.launch(True, False)}
         self._graphs = {}
-        with torch.cuda.stream(side):
+        with c.capturing() as graph:
             keep = [(t, t.clone()) for t in (self.norm._f64, self.norm.slot, self.norm.reward, self.norm.bad_masks, act_step.masks,
                                              img_feat, goal_feat)]
             for key, fn in bodies.items():
                 self.norm.slot.fill_(-2)                         # the warm-up's insert selects no slot: the storage stays as it is
-                fn()                                             # warm-up outside capture (lazy kernel attributes)
-                g = new_graph()
-                with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                    fn()
-                self._graphs[key] = g
+                self._graphs[key] = graph(fn, warm=True)
             for t, saved in keep:                                # what the warm-up touched: ret, rms, episode, slot, the buffers
                 t.copy_(saved)
             self.norm.slot.copy_(torch.tensor([rollouts.step, rollouts.step], dtype=torch.int32))
-        torch.cuda.current_stream().wait_stream(side)
         self._slot = rollouts.step                               # host mirror of slot[0]
         self._have_goal = False
         # pinned staging: image | extras | goal sound | current sound (sound-sound) | env_reward, done, bad -- each 16-byte aligned
@@ -420,13 +354,6 @@ class CollectStep:
         self._event_live = True
 
     # ---- the step ---------------------------------------------------------------------------------------------------------------
-    def _ids_value(self, ids, name, keep):
-        """One id argument with a clip table: an int32 device tensor as it is (a bad id there is the kernel's NaN rule), anything
-        else range-checked on the host -- before anything is staged."""
-        if torch.is_tensor(ids) and ids.is_cuda:
-            return ids
-        return self.clip_table.host_ids(ids, "CollectStep: " + name, self.num_envs, keep)
-
     @torch.no_grad()
     def reset(self, image, extras, goal_sound=None, goal_ids=None):
         """envs.reset() + RL.py:137-141: embeds the first observation (the goal sound with it), writes the observations to
@@ -438,11 +365,11 @@ class CollectStep:
         if self.clip_table is not None:
             if goal_ids is None or goal_sound is not None:
                 raise VarHipError("CollectStep.reset: built with a clip table -- the goal of every env comes as goal_ids")
-            goal_ids = self._ids_value(goal_ids, "goal_ids", False)
+            goal_ids = self.clip_table.ids(goal_ids, "CollectStep: goal_ids", self.num_envs)
             small = [('goal_ids', goal_ids, self.goal_ids)]
             plans = self._plans(image, extras, None, small)
             self._stage_inputs(plans, ('goal_ids',))
-            self._goal_set[:] = True
+            self._reward_step.goal_set[:] = True
         else:
             if goal_sound is None:
                 raise VarHipError("CollectStep.reset: the goal sound of the episode is required")
@@ -499,21 +426,19 @@ class CollectStep:
         if self.sound_sound and current_ids is None:
             raise VarHipError("CollectStep.observe: the reward has sound_sound on -- every step needs current_ids "
                               "(vec_pretext_normalize.py:82-95; clip_table.silent when nothing is heard)")
-        goal = self._keep_ids if goal_ids is None else self._ids_value(goal_ids, "goal_ids", True)
-        kept = np.zeros(self.num_envs, bool) if torch.is_tensor(goal) else goal == -1
-        if (kept & ~self._goal_set).any():
-            raise VarHipError("CollectStep.observe: no goal embedding is cached yet for envs "
-                              f"{np.nonzero(kept & ~self._goal_set)[0].tolist()} -- reset() or pass their goal ids")
+        ids = lambda a, name, keep: self.clip_table.ids(a, "CollectStep: " + name, self.num_envs, keep)   # noqa: E731
+        goal = self._keep_ids if goal_ids is None else ids(goal_ids, "goal_ids", True)
+        kept = self._reward_step.kept_goals(goal, "CollectStep.observe", "reset() or pass their goal ids")
         if bad is None:
             bad = self._zero_bad()
         small = [('env_reward', env_reward, self.env_reward), ('goal_ids', goal, self.goal_ids)]
         if self.sound_sound:
-            small.append(('current_ids', self._ids_value(current_ids, "current_ids", False), self.current_ids))
+            small.append(('current_ids', ids(current_ids, "current_ids", False), self.current_ids))
         small += [('done', done, self.done), ('bad', bad, self.bad)]
         plans = self._plans(image, extras, None, small)
         self._stage_inputs(plans, tuple(name for name, _, _ in small))
         self._graphs["step"].replay()
-        self._goal_set |= ~kept
+        self._reward_step.goal_set |= ~kept
         self._slot = self.rollouts.step = (self._slot + 1) % self.rollouts.num_steps
         return self.norm.reward
 

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ._lib import Context, VarHipError, current_stream_handle, new_graph, ptr
+from ._lib import Context, VarHipError, current_stream_handle, ptr
 
 
 class _IthorFn(torch.autograd.Function):
@@ -382,25 +382,15 @@ class IthorTrainer:
                     "var_adam_step_dev")
 
         collective = self.world > 1 or getattr(self, "rccl", None) is not None
-        side = torch.cuda.Stream(device=self.dev)
-        side.wait_stream(torch.cuda.current_stream())
-        graphs = []
-        with torch.cuda.stream(side):
-            for bodies in ((body_grad,), (body_adam,)) if collective else ((body_grad, body_adam),):
-                g = new_graph()
-                with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                    for b in bodies:
-                        b()
-                graphs.append(g)
-        torch.cuda.current_stream().wait_stream(side)
+        graphs = c.capture(((body_grad,), (body_adam,)) if collective else ((body_grad, body_adam),))
         self._keep = getattr(self, "_keep_all", []) + [(image, pcm, lens, feats, graphs)]
         self._keep_all = self._keep
 
         def replay():
-            graphs[0].replay()
+            graphs[0]()
             if collective:
                 self.allreduce()
-                graphs[1].replay()
+                graphs[1]()
             return self.loss
         return replay
 

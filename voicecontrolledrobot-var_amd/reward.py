@@ -8,7 +8,8 @@ forward is the HIP path (VARPretextNet.forward); the rest is host arithmetic on 
 as in the reference.  IntrinsicReward(model, sound_sound=True) is config.RLRewardSoundSound: the current sound of every step
 is embedded too and <current_sound_feat, goal_sound_feat> joins the reward, on the eager pair embeddings() / reward() and on the
 captured step().  build_clip_table() embeds a pool of clips once per checkpoint (ClipTable); capture(batch, clip_table=table)
-then takes clip indices instead of feature arrays (step_ids): no sound branch on the step, the goal cached per env.
+then takes clip indices instead of feature arrays (step_ids): no sound branch on the step, the goal cached per env.  Which C
+entries a captured step is made of, route by route, is reward_step.py's business (RewardStep); this module owns the buffers.
 """
 import numpy as np
 import torch
@@ -102,6 +103,11 @@ class ClipTable:
                               f"silence{', -1 keeps the cached goal' if keep else ''}): {a.tolist()}")
         return a.astype(np.int32)
 
+    def ids(self, ids, name, batch, keep=False):
+        """One id argument of a step: an int32 device tensor as it is (a bad id there is the kernel's NaN rule), anything else
+        range-checked on the host (host_ids) -- before anything is staged or copied."""
+        return ids if torch.is_tensor(ids) and ids.is_cuda else self.host_ids(ids, name, batch, keep)
+
 
 CLIP_CHUNK = 256        # clips embedded per call of build_clip_table: at most 25 MB (Kuka: 4) of features beside the table
 
@@ -147,6 +153,7 @@ class IntrinsicReward:
         mfcc_pos alone, save_for_bwd = 2.  A row's bits do not depend on `chunk` or on its neighbours."""
         from ._lib import Context, VarHipError, current_stream_handle, ptr
         from .ithor import IthorVARPretextNet
+        from .reward_step import prepare
         from . import ops
         m = self.model
         flat = m.flat_parameters()
@@ -174,14 +181,7 @@ class IntrinsicReward:
                 raise VarHipError(f"IntrinsicReward.build_clip_table: lens has shape {tuple(lens.shape)}, expected ({rows},)")
         ithor = isinstance(m, IthorVARPretextNet)
         c = Context.get(dev.index)
-        if ithor:
-            if flat.numel() != c.lib.var_ithor_param_count():
-                raise VarHipError("parameter arena does not match var_ithor_param_count()")
-            c.check(c.lib.var_ithor_reward_plan(c.handle, 16, int(m.config.img_dim[1])), "var_ithor_reward_plan")
-            c.check(c.lib.var_ithor_reward_pack(c.handle, current_stream_handle(), ptr(flat)), "var_ithor_reward_pack")
-        else:
-            c.ensure_plan(min(chunk, rows + 1), int(m.config.img_dim[1]))
-            w = m.hip_weights(c, force=True)
+        w = prepare(c, m, flat, 16 if ithor else min(chunk, rows + 1))
         feat = torch.empty((rows + 1, self.rep), dtype=torch.float32, device=dev)
 
         def embed(x, out):
@@ -205,81 +205,68 @@ class IntrinsicReward:
         return ClipTable(feat, m)
 
     # ---- latency path: the whole frozen-encoder step as a replayed HIP graph --------------------------------
-    def _capture_ids(self, batch, table):
-        """capture(batch, clip_table=table): ONE graph over static id buffers -- the image stack and one gather-and-dot launch
-        (iTHOR: var_ithor_reward_step_ids, 7 kernels; Kuka: an image-only var_arm_encoder_fwd + var_reward_dots_ids)."""
-        from ._lib import Context, VarHipError, current_stream_handle, new_graph, ptr
+    def capture(self, batch, clip_table=None):
+        """Capture the frozen encoder for a fixed number of envs (BASELINE config 5: 8) into two HIP graphs --
+        image + goal sound (first step of an episode) and image only (later steps: the goal embedding is reused) --
+        over static device buffers; the launches of each are reward_step.RewardStep's.  Weights are packed once here:
+        call again after loading another checkpoint.  Returns self; then use step().
+
+        For an IthorVARPretextNet (96 x 96 images, at most 64 envs) the arena is snapshotted, so the graphs follow the
+        weights the model had at this call until capture() is called again.  The goal embedding is cached for the WHOLE
+        batch (pretext_base.py:26-32: every env resets at the same time); step(image, None) before any goal step raises.
+
+        With sound_sound (config.RLRewardSoundSound) both graphs also embed the current sound of every step and the reward
+        is calcReward's <image_feat, goal_feat> + <current_sound_feat, goal_feat> (var_reward_dots' grouping).  Further
+        static buffers, as attributes: current_sound (B,) + sound_dim, cur_feat (B,3), img_sound_dot and sound_sound_dot (B,).
+
+        With clip_table (build_clip_table) the sounds arrive as clip indices: ONE graph, no sound branch in it, static int32
+        buffers goal_ids / current_ids (B,), and step_ids() instead of step().  Without it everything is as above."""
+        from ._lib import Context, VarHipError
         from .ithor import IthorVARPretextNet
-        if not isinstance(table, ClipTable):
+        from .reward_step import RewardStep
+        m, table, B, ss = self.model, clip_table, int(batch), bool(self.sound_sound)
+        dev = m.flat_parameters().device
+        if dev.type != "cuda":
+            raise VarHipError("IntrinsicReward.capture needs the model on the GPU (no CPU fallback)")
+        if table is not None and not isinstance(table, ClipTable):
             raise VarHipError("IntrinsicReward.capture: clip_table must be a ClipTable (build_clip_table)")
-        m = self.model
-        table.check(m)
-        flat = m.flat_parameters()
-        dev = flat.device
-        c = Context.get(dev.index)
-        hw = int(m.config.img_dim[1])
-        B = int(batch)
-        ss = bool(self.sound_sound)
-        ithor = isinstance(m, IthorVARPretextNet)
-        if table.dim != 3 or table.feat.device != dev:
+        if table is not None and (table.dim != 3 or table.feat.device != dev):
             raise VarHipError("IntrinsicReward.capture: the clip table is not this model's (dimension or device)")
-        if ithor:
-            c.check(c.lib.var_ithor_reward_plan(c.handle, B, hw), "var_ithor_reward_plan")
-            c.check(c.lib.var_ithor_reward_pack(c.handle, current_stream_handle(), ptr(flat)), "var_ithor_reward_pack")
+        zeros = lambda *shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)   # noqa: E731
+        self._B, self._table, self._ithor = B, table, isinstance(m, IthorVARPretextNet)
+        self._have_goal = False
+        self._img = zeros(B, *m.config.img_dim, dtype=torch.uint8)
+        self._image_feat, self._goal_feat, self._reward = zeros(B, 3), zeros(B, 3), zeros(B)
+        self.current_sound = None                                # (set by a capture with sound_sound and no table)
+        if table is None:
+            self._goal = zeros(B, *m.config.sound_dim)
+            goal, cur = self._goal, None
+            if ss:
+                cur = self.current_sound = zeros(B, *m.config.sound_dim)
         else:
-            c.ensure_plan(B, hw)
-            w = m.hip_weights(c, force=True)
-        self._B, self._table, self._ithor = B, table, ithor
-        self._img = torch.zeros((B,) + tuple(m.config.img_dim), dtype=torch.uint8, device=dev)
-        self._image_feat = torch.zeros((B, 3), device=dev)
-        self._goal_feat = torch.zeros((B, 3), device=dev)
-        self._reward = torch.zeros((B,), device=dev)
-        self._ids = torch.full((2, B), -1, dtype=torch.int32, device=dev)
-        self.goal_ids, self.current_ids = self._ids[0], self._ids[1]
-        self.current_ids.fill_(table.silent)
-        self._goal_set = np.zeros(B, bool)                       # per env: has a goal embedding been cached?
-        self.current_sound = None
+            self._ids = torch.full((2, B), -1, dtype=torch.int32, device=dev)
+            goal, cur = self.goal_ids, self.current_ids = self._ids[0], self._ids[1]
+            cur.fill_(table.silent)
         if ss:
-            self.cur_feat = torch.zeros((B, 3), device=dev)
-            self.img_sound_dot = torch.zeros((B,), device=dev)
-            self.sound_sound_dot = torch.zeros((B,), device=dev)
-        cur = dict(ids=ptr(self.current_ids), feat=ptr(self.cur_feat), img=ptr(self.img_sound_dot),
-                   snd=ptr(self.sound_sound_dot)) if ss else dict(ids=None, feat=None, img=None, snd=None)
-
-        def body():
-            if ithor:
-                c.check(c.lib.var_ithor_reward_step_ids(c.handle, current_stream_handle(), ptr(flat), ptr(self._img), 1,
-                                                        self._img.stride(0), ptr(table.feat), table.rows + 1, ptr(self.goal_ids),
-                                                        cur["ids"], B, ptr(self._image_feat), ptr(self._goal_feat), cur["feat"],
-                                                        ptr(self._reward), cur["img"], cur["snd"]), "var_ithor_reward_step_ids")
-                return
-            w.bind()
-            c.check(c.lib.var_arm_encoder_fwd(c.handle, current_stream_handle(), ptr(flat), ptr(self._img), 1, self._img.stride(0),
-                                              None, None, B, hw, ptr(self._image_feat), None, None, None, None, 2),
-                    "var_arm_encoder_fwd")
-            c.check(c.lib.var_reward_dots_ids(c.handle, current_stream_handle(), ptr(self._image_feat), ptr(table.feat),
-                                              table.rows + 1, ptr(self.goal_ids), cur["ids"], ptr(self._goal_feat), cur["feat"], B, 3,
-                                              ptr(self._reward), cur["img"], cur["snd"]), "var_reward_dots_ids")
-
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            body()                                               # warm-up outside capture (lazy kernel attributes)
-            g = new_graph()
-            with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                body()
-            self._graphs = {"ids": g}
-        torch.cuda.current_stream().wait_stream(side)
+            self.cur_feat, self.img_sound_dot, self.sound_sound_dot = zeros(B, 3), zeros(B), zeros(B)
+        c = Context.get(dev.index)
+        more = dict(cur_feat=self.cur_feat, reward_img=self.img_sound_dot, reward_snd=self.sound_sound_dot) if ss else {}
+        rs = self._step = RewardStep(c, m, B, image=self._img, is_u8=1, goal=goal, cur=cur, image_feat=self._image_feat,
+                                     goal_feat=self._goal_feat, reward=self._reward, sound_sound=ss, clip_table=table, **more)
+        keys = {"ids": True} if table is not None else {True: True, False: False}       # graph -> its with_goal
+        with c.capturing() as graph:
+            self._graphs = {key: graph(lambda g=with_goal: rs.launch(g, ss), warm=True) for key, with_goal in keys.items()}
+            if self._ithor and table is None:
+                self._goal_feat.zero_()                          # (the warm-up's embedding of the all-zero buffer is no goal)
         return self
 
     def _ids_input(self, ids, name, keep):
-        """One id argument of step_ids: ('host', checked int32 array) or ('dev', int32 tensor); refuses everything else."""
+        """One id argument of step_ids (ClipTable.ids); an int32 tensor on the device must be this step's shape and device."""
         from ._lib import VarHipError
-        if torch.is_tensor(ids) and ids.is_cuda:
-            if ids.dtype != torch.int32 or tuple(ids.shape) != (self._B,) or ids.device != self._ids.device:
-                raise VarHipError(f"IntrinsicReward.step_ids: {name} on the device must be int32 ({self._B},) on {self._ids.device}")
-            return 'dev', ids
-        return 'host', self._table.host_ids(ids, "IntrinsicReward.step_ids: " + name, self._B, keep)
+        ids = self._table.ids(ids, "IntrinsicReward.step_ids: " + name, self._B, keep)
+        if torch.is_tensor(ids) and (ids.dtype != torch.int32 or tuple(ids.shape) != (self._B,) or ids.device != self._ids.device):
+            raise VarHipError(f"IntrinsicReward.step_ids: {name} on the device must be int32 ({self._B},) on {self._ids.device}")
+        return ids
 
     def step_ids(self, image_u8, goal_ids=None, current_ids=None):
         """One env step of a capture(batch, clip_table=table): clip indices instead of feature arrays.  goal_ids (B): a clip's
@@ -297,12 +284,9 @@ class IntrinsicReward:
         if ss and current_ids is None:
             raise VarHipError("IntrinsicReward.step_ids: sound_sound is on -- every step needs current_ids "
                               "(vec_pretext_normalize.py:82-95; table.silent when nothing is heard)")
-        goal = ('host', np.full(self._B, -1, np.int32)) if goal_ids is None else self._ids_input(goal_ids, "goal_ids", True)
+        goal = np.full(self._B, -1, np.int32) if goal_ids is None else self._ids_input(goal_ids, "goal_ids", True)
         ids = [goal] + ([self._ids_input(current_ids, "current_ids", False)] if ss else [])
-        kept = goal[1] == -1 if goal[0] == 'host' else np.zeros(self._B, bool)
-        if (kept & ~self._goal_set).any():
-            raise VarHipError("IntrinsicReward.step_ids: no goal embedding is cached yet for envs "
-                              f"{np.nonzero(kept & ~self._goal_set)[0].tolist()} -- pass their goal ids (pretext_base.py:26-32)")
+        kept = self._step.kept_goals(goal, "IntrinsicReward.step_ids", "pass their goal ids (pretext_base.py:26-32)")
         image_u8 = torch.as_tensor(image_u8)
         if tuple(image_u8.shape) != tuple(self._img.shape) or image_u8.dtype != torch.uint8:
             raise VarHipError(f"IntrinsicReward.step_ids: image is {image_u8.dtype} {tuple(image_u8.shape)}, expected uint8 "
@@ -310,199 +294,24 @@ class IntrinsicReward:
         if self._ithor and not image_u8.is_cuda:
             raise VarHipError("IntrinsicReward.step_ids: image must be a CUDA tensor (no CPU fallback)")
         self._img.copy_(image_u8, non_blocking=True)
-        if all(kind == 'host' for kind, _ in ids):               # one copy for both
-            self._ids[:len(ids)].copy_(torch.from_numpy(np.stack([a for _, a in ids])), non_blocking=True)
+        if not any(torch.is_tensor(a) for a in ids):             # all from the host: one copy for both
+            self._ids[:len(ids)].copy_(torch.from_numpy(np.stack(ids)), non_blocking=True)
         else:
-            for buf, (kind, a) in zip(self._ids, ids):
-                buf.copy_(a if kind == 'dev' else torch.from_numpy(a), non_blocking=True)
-        self._goal_set |= ~kept
+            for buf, a in zip(self._ids, ids):
+                buf.copy_(a if torch.is_tensor(a) else torch.from_numpy(a), non_blocking=True)
         self._graphs["ids"].replay()
+        self._step.goal_set |= ~kept
         return self._image_feat, self._goal_feat, self._reward
 
-    def capture(self, batch, clip_table=None):
-        """Capture the frozen encoder for a fixed number of envs (BASELINE config 5: 8) into two HIP graphs --
-        image + goal sound (first step of an episode) and image only (later steps: the goal embedding is reused) --
-        over static device buffers.  Weights are packed once here: call again after loading another checkpoint.
-        Returns self; then use step().
-
-        For an IthorVARPretextNet the step is var_ithor_reward_step (96 x 96 images, at most 64 envs): the arena is
-        snapshotted and its convolutions packed once here, so the graphs follow the weights the model had at this call
-        until capture() is called again.  The goal embedding is cached for the WHOLE batch (pretext_base.py:26-32:
-        every env resets at the same time); step(image, None) before any goal step raises.
-
-        With sound_sound (config.RLRewardSoundSound) both graphs also embed the current sound of every step and the reward
-        is calcReward's <image_feat, goal_feat> + <current_sound_feat, goal_feat> (var_reward_dots' grouping).  Further
-        static buffers, as attributes: current_sound (B,) + sound_dim, cur_feat (B,3), img_sound_dot and sound_sound_dot
-        (B,).  The Kuka encoder takes the current sound as var_arm_encoder_fwd's mfcc_neg and var_reward_dots follows the
-        forward (var_set_reward_dot is not armed); the iTHOR encoder is var_ithor_reward_step_ex.
-
-        With clip_table (build_clip_table) the sounds arrive as clip indices: ONE graph, no sound branch in it, static int32
-        buffers goal_ids / current_ids (B,), and step_ids() instead of step().  Without it everything is as above."""
-        from ._lib import Context, current_stream_handle, new_graph, ptr
-        if clip_table is not None:
-            return self._capture_ids(batch, clip_table)
-        m = self.model
-        from .ithor import IthorVARPretextNet
-        self.current_sound = None                # (set by a capture with sound_sound)
-        if isinstance(m, IthorVARPretextNet):
-            return self._capture_ithor(batch)
-        flat = m.flat_parameters()
-        dev = flat.device
-        c = Context.get(dev.index)
-        hw = m.config.img_dim[1]
-        B = int(batch)
-        c.ensure_plan(B, hw)
-        self._B = B
-        self._img = torch.zeros((B, 3, hw, hw), dtype=torch.uint8, device=dev)
-        self._goal = torch.zeros((B, 1, 100, 40), dtype=torch.float32, device=dev)
-        self._image_feat = torch.zeros((B, 3), device=dev)
-        self._goal_feat = torch.zeros((B, 3), device=dev)
-        self._reward = torch.zeros((B,), device=dev)
-        ss = bool(self.sound_sound)
-        if ss:
-            self._sound_sound_buffers(B, (1, 100, 40), dev)
-        w = m.hip_weights(c, force=True)        # the frozen model's own packed image; the graphs keep its address
-
-        def body(with_goal):
-            w.bind()
-            if ss:
-                # the current sound rides as the forward's negative clip; both dots and their sum are one launch behind it
-                c.check(c.lib.var_arm_encoder_fwd(c.handle, current_stream_handle(), ptr(flat), ptr(self._img), 1,
-                                                  self._img.stride(0), ptr(self._goal) if with_goal else None,
-                                                  ptr(self.current_sound), B, hw, ptr(self._image_feat),
-                                                  ptr(self._goal_feat) if with_goal else None, ptr(self.cur_feat),
-                                                  None, None, 2), "var_arm_encoder_fwd")
-                c.check(c.lib.var_reward_dots(c.handle, current_stream_handle(), ptr(self._image_feat), ptr(self._goal_feat),
-                                              ptr(self.cur_feat), B, self._image_feat.shape[1], ptr(self._reward),
-                                              ptr(self.img_sound_dot), ptr(self.sound_sound_dot)), "var_reward_dots")
-                return
-            if not with_goal:
-                # the goal embedding is cached: the forward itself leaves <image_feat, goal_feat> (var_set_reward_dot)
-                c.check(c.lib.var_set_reward_dot(c.handle, ptr(self._goal_feat), ptr(self._reward)), "var_set_reward_dot")
-            c.check(c.lib.var_arm_encoder_fwd(c.handle, current_stream_handle(), ptr(flat), ptr(self._img), 1,
-                                              self._img.stride(0), ptr(self._goal) if with_goal else None, None, B, hw,
-                                              ptr(self._image_feat), ptr(self._goal_feat) if with_goal else None,
-                                              None, None, None, 2), "var_arm_encoder_fwd")      # 2: inference, small-batch kernels
-            if not with_goal:
-                return
-            # <image_feat, goal_feat> (calcReward's torch.sum(a * b, dim=1): one launch instead of a product and a reduction)
-            c.check(c.lib.var_row_dot(c.handle, current_stream_handle(), ptr(self._image_feat), ptr(self._goal_feat), B,
-                                      self._image_feat.shape[1], ptr(self._reward)), "var_row_dot")
-
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
-        self._graphs = {}
-        with torch.cuda.stream(side):
-            for with_goal in (True, False):
-                body(with_goal)                                  # warm-up outside capture (lazy kernel attributes)
-                g = new_graph()
-                with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                    body(with_goal)
-                self._graphs[with_goal] = g
-        torch.cuda.current_stream().wait_stream(side)
-        return self
-
-    def _capture_ithor(self, batch):
-        from ._lib import Context, VarHipError, current_stream_handle, new_graph, ptr
-        m = self.model
-        flat = m.flat_parameters()
-        dev = flat.device
-        if not flat.is_cuda:
-            raise VarHipError("IntrinsicReward.capture needs the model on the GPU (no CPU fallback)")
-        c = Context.get(dev.index)
-        if flat.numel() != c.lib.var_ithor_param_count():
-            raise VarHipError("parameter arena does not match var_ithor_param_count()")
-        hw = m.config.img_dim[1]
-        B = int(batch)
-        ss = bool(self.sound_sound)
-        c.check(c.lib.var_ithor_reward_plan_ex(c.handle, B, int(hw), int(ss)), "var_ithor_reward_plan_ex")
-        c.check(c.lib.var_ithor_reward_pack(c.handle, current_stream_handle(), ptr(flat)), "var_ithor_reward_pack")
-        self._B = B
-        self._ithor = True
-        self._have_goal = False
-        self._img = torch.zeros((B,) + tuple(m.config.img_dim), dtype=torch.uint8, device=dev)
-        self._goal = torch.zeros((B,) + tuple(m.config.sound_dim), dtype=torch.float32, device=dev)
-        self._image_feat = torch.zeros((B, 3), device=dev)
-        self._goal_feat = torch.zeros((B, 3), device=dev)
-        self._reward = torch.zeros((B,), device=dev)
-        if ss:
-            self._sound_sound_buffers(B, tuple(m.config.sound_dim), dev)
-
-        def body(with_goal):
-            if ss:
-                c.check(c.lib.var_ithor_reward_step_ex(c.handle, current_stream_handle(), ptr(flat), ptr(self._img), 1,
-                                                       self._img.stride(0), ptr(self._goal) if with_goal else None,
-                                                       ptr(self.current_sound), B, ptr(self._image_feat), ptr(self._goal_feat),
-                                                       ptr(self.cur_feat), ptr(self._reward), ptr(self.img_sound_dot),
-                                                       ptr(self.sound_sound_dot)), "var_ithor_reward_step_ex")
-                return
-            c.check(c.lib.var_ithor_reward_step(c.handle, current_stream_handle(), ptr(flat), ptr(self._img), 1,
-                                                self._img.stride(0), ptr(self._goal) if with_goal else None, B,
-                                                ptr(self._image_feat), ptr(self._goal_feat), ptr(self._reward)),
-                    "var_ithor_reward_step")
-
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
-        self._graphs = {}
-        with torch.cuda.stream(side):
-            for with_goal in (True, False):
-                body(with_goal)                                  # warm-up outside capture (lazy kernel attributes)
-                g = new_graph()
-                with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                    body(with_goal)
-                self._graphs[with_goal] = g
-            self._goal_feat.zero_()                              # (the warm-up's embedding of the all-zero buffer is no goal)
-        torch.cuda.current_stream().wait_stream(side)
-        return self
-
-    def _sound_sound_buffers(self, B, sound_dim, dev):
-        self.current_sound = torch.zeros((B,) + tuple(sound_dim), dtype=torch.float32, device=dev)
-        self.cur_feat = torch.zeros((B, 3), device=dev)
-        self.img_sound_dot = torch.zeros((B,), device=dev)
-        self.sound_sound_dot = torch.zeros((B,), device=dev)
-
-    def _check_current(self, current_sound, cuda_only):
-        """The current sound of a sound-sound step as a tensor, refused before anything is copied or replayed."""
+    def _checked(self, value, buf, name, strict):
+        """One input of step() as a tensor; strict (iTHOR): a CUDA tensor of the buffer's shape, or a refusal."""
         from ._lib import VarHipError
-        if current_sound is None:
-            raise VarHipError("IntrinsicReward.step: sound_sound is on -- every step needs current_sound "
-                              "(vec_pretext_normalize.py:82-95)")
-        current_sound = torch.as_tensor(current_sound)
-        if cuda_only and not current_sound.is_cuda:
-            raise VarHipError("IntrinsicReward.step: current_sound must be a CUDA tensor (no CPU fallback)")
-        if tuple(current_sound.shape) != tuple(self.current_sound.shape):
-            raise VarHipError(f"IntrinsicReward.step: current_sound shape {tuple(current_sound.shape)} is not "
-                              f"{tuple(self.current_sound.shape)}")
-        return current_sound
-
-    def _step_ithor(self, image_u8, goal_sound, current_sound=None):
-        from ._lib import VarHipError
-        ss = getattr(self, "current_sound", None) is not None
-        if ss:
-            current_sound = self._check_current(current_sound, True)
-        image_u8 = torch.as_tensor(image_u8)
-        if not image_u8.is_cuda:
-            raise VarHipError("IntrinsicReward.step: image must be a CUDA tensor (no CPU fallback)")
-        if tuple(image_u8.shape) != tuple(self._img.shape):
-            raise VarHipError(f"IntrinsicReward.step: image shape {tuple(image_u8.shape)} is not {tuple(self._img.shape)}")
-        if goal_sound is not None:
-            goal_sound = torch.as_tensor(goal_sound)
-            if not goal_sound.is_cuda:
-                raise VarHipError("IntrinsicReward.step: goal_sound must be a CUDA tensor (no CPU fallback)")
-            if tuple(goal_sound.shape) != tuple(self._goal.shape):
-                raise VarHipError(f"IntrinsicReward.step: goal_sound shape {tuple(goal_sound.shape)} is not "
-                                  f"{tuple(self._goal.shape)}")
-        elif not self._have_goal:
-            raise VarHipError("IntrinsicReward.step: no goal embedding is cached yet -- pass goal_sound on the first "
-                              "step of an episode (pretext_base.py:26-32)")
-        self._img.copy_(image_u8, non_blocking=True)
-        if goal_sound is not None:
-            self._goal.copy_(goal_sound, non_blocking=True)
-            self._have_goal = True
-        if ss:
-            self.current_sound.copy_(current_sound, non_blocking=True)
-        self._graphs[goal_sound is not None].replay()
-        return self._image_feat, self._goal_feat, self._reward
+        value = torch.as_tensor(value)
+        if strict and not value.is_cuda:
+            raise VarHipError(f"IntrinsicReward.step: {name} must be a CUDA tensor (no CPU fallback)")
+        if (strict or buf is self.current_sound) and tuple(value.shape) != tuple(buf.shape):
+            raise VarHipError(f"IntrinsicReward.step: {name} shape {tuple(value.shape)} is not {tuple(buf.shape)}")
+        return value
 
     def step(self, image_u8, goal_sound=None, current_sound=None):
         """One env step of `batch` envs: copies the observations into the static buffers and replays the graph.
@@ -510,15 +319,25 @@ class IntrinsicReward:
         reward is <image_feat, goal_feat>; captured with sound_sound it is that plus <cur_feat, goal_feat> (the two terms
         stay in img_sound_dot / sound_sound_dot, the current sound's embedding in cur_feat) and every step needs
         current_sound -- without it the step raises before anything is copied or replayed.  Captured without sound_sound,
-        current_sound is ignored, as embeddings() ignores it."""
-        if getattr(self, "_ithor", False):
-            return self._step_ithor(image_u8, goal_sound, current_sound)
-        if getattr(self, "current_sound", None) is not None:
-            current_sound = self._check_current(current_sound, False)
-            self.current_sound.copy_(current_sound, non_blocking=True)
-        self._img.copy_(torch.as_tensor(image_u8), non_blocking=True)
+        current_sound is ignored, as embeddings() ignores it.  The iTHOR step takes CUDA tensors of the buffers' shapes only and
+        refuses a step without any goal; the Kuka step copies what it is given, host arrays included."""
+        from ._lib import VarHipError
+        strict = self._ithor
+        ss = self.current_sound is not None
+        if ss and current_sound is None:
+            raise VarHipError("IntrinsicReward.step: sound_sound is on -- every step needs current_sound "
+                              "(vec_pretext_normalize.py:82-95)")
+        copies = [(self._img, self._checked(image_u8, self._img, "image", strict))]
         if goal_sound is not None:
-            self._goal.copy_(torch.as_tensor(goal_sound), non_blocking=True)
+            copies.append((self._goal, self._checked(goal_sound, self._goal, "goal_sound", strict)))
+        elif strict and not self._have_goal:
+            raise VarHipError("IntrinsicReward.step: no goal embedding is cached yet -- pass goal_sound on the first "
+                              "step of an episode (pretext_base.py:26-32)")
+        if ss:
+            copies.append((self.current_sound, self._checked(current_sound, self.current_sound, "current_sound", strict)))
+        for buf, value in copies:
+            buf.copy_(value, non_blocking=True)
+        self._have_goal |= goal_sound is not None
         self._graphs[goal_sound is not None].replay()
         return self._image_feat, self._goal_feat, self._reward
 
