@@ -364,6 +364,24 @@ int var_inbatch_loss_fwd_bwd(var_ctx* ctx, void* stream, const float* anchor, co
                              int B, int M, float tau, float inv_count, float* scratch, float* loss_out,
                              float* g_anchor, float* g_cand);
 
+/* The class-aware forms of the head above (which ignores labels: with taskNum + 1 classes about a fifth of an anchor's other
+ * candidates carry the anchor's own class and are pushed away as negatives; the triplet loss never draws such a negative,
+ * dataset.py:70-78).  anchor_cls (B) = y_i, cand_cls (M) = z_j, int32 on the device; l_ij = -d_ij / tau, t(i) = target[i]:
+ *   VAR_INBATCH_ALL             L_i = logsumexp_j l_ij - l_{i,t(i)}: var_inbatch_loss_fwd_bwd bit for bit; the class pointers
+ *                               are not read and may be NULL.
+ *   VAR_INBATCH_OTHER_CLASS     L_i = logsumexp_{j in N_i} l_ij - l_{i,t(i)},  N_i = { j : z_j != y_i } + { t(i) }: the other
+ *                               candidates of the anchor's class take no part, in the sum or in any gradient.
+ *   VAR_INBATCH_MULTI_POSITIVE  L_i = logsumexp_j l_ij - (1/|P_i|) sum_{p in P_i} l_ip,  P_i = { j : z_j = y_i } + { t(i) }
+ *                               (the supervised-contrastive form with the positives outside the log).
+ * loss_out[0] = inv_count * sum_i L_i; gradients and their use under data parallelism as above.  z_{t(i)} = y_i is not
+ * required; target[i] in [0, M) is the caller's duty.  scratch: 3*B floats.  A mode whose masks select nothing (no class
+ * shared) gives the bits of mode 0.  VAR_ERR_ARG, nothing written: what the entry above refuses, a mode outside 0..2, a NULL
+ * class pointer in mode 1 or 2. */
+enum { VAR_INBATCH_ALL = 0, VAR_INBATCH_OTHER_CLASS = 1, VAR_INBATCH_MULTI_POSITIVE = 2 };
+int var_inbatch_loss_fwd_bwd_ex(var_ctx* ctx, void* stream, const float* anchor, const float* cand, const int* target,
+                                const int* anchor_cls, const int* cand_cls, int B, int M, float tau, float inv_count,
+                                int mode, float* scratch, float* loss_out, float* g_anchor, float* g_cand);
+
 /* Collectives ----------------------------------------------------------------------------------
  * For hosts without torch.distributed: one RCCL communicator per context.  Rank 0 obtains a 128-byte unique id
  * (var_comm_unique_id), the host ships it to the other ranks over its own channel, every rank calls var_comm_init.

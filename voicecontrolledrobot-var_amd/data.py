@@ -159,6 +159,13 @@ class TripletPool:
         self._cursor = 0
         return self
 
+    def class_tables(self):
+        """(gt (N), sn (N)) as contiguous int32 device tensors: the class of each item's positive and negative clip, for the
+        class-aware in-batch head (VARTrainer.step_inbatch(classes=...)).  "Empty" is class task_num, a class like any other."""
+        if getattr(self, "_class_tabs", None) is None:
+            self._class_tabs = (self.gt.to(torch.int32).contiguous(), self.sn.to(torch.int32).contiguous())
+        return self._class_tabs
+
     def next_batch_indices(self, batch):
         """(image_index (B), clip_index (2B), lens (2B)) int32 for the next shuffled batch; 2 small gathers."""
         if self._perm is None or self._cursor + batch > self.n_items:

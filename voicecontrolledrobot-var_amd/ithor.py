@@ -326,6 +326,62 @@ class IthorTrainer:
         self.adam()
         return self.loss
 
+    def step_inbatch(self, image, pos, neg, tau=0.1, classes=None, negatives="all"):
+        """One optimisation step with the in-batch-negatives contrastive head instead of the triplet loss, as
+        VARTrainer.step_inbatch (the embedding dim is 3 in both models): var_ithor_encoder_fwd, all-gather of every rank's
+        [positive ; negative] sound embeddings, the head (csrc/inbatch.hip), one small all-reduce of the candidate gradients,
+        var_ithor_encoder_bwd on the rank's own rows, then this trainer's all-reduce, guard and Adam.  Eager only.
+        classes = (gt (B), sn (B)) int32 with negatives = "other_class" | "multi_positive" (include/var_hip.h:
+        var_inbatch_loss_fwd_bwd_ex); their [gt ; sn] is all-gathered like the embeddings.  Equal shards."""
+        from .ops import check_classes, inbatch_contrastive_loss, inbatch_mode
+        m, c = self.model, self.ctx
+        flat = m.flat_parameters()
+        for t in (image, pos, neg):
+            if t is None or not t.is_cuda:
+                raise VarHipError("IthorTrainer needs CUDA tensors (image, pos, neg) -- no CPU fallback")
+        B = image.shape[0]
+        mode = inbatch_mode(negatives, classes is not None)
+        if classes is not None:
+            gt, sn = (check_classes(t, B, self.dev, "classes = (gt, sn): each") for t in classes)
+        m._ensure_plan(c, B)
+        if image.dtype != torch.uint8:
+            image = image.float()
+        image, pos, neg = image.contiguous(), pos.float().contiguous(), neg.float().contiguous()
+        dev, rank, world, rccl = self.dev, self.rank, self.world, getattr(self, "rccl", None)
+        stream = current_stream_handle()
+        emb = torch.empty((3, B, 3), dtype=torch.float32, device=dev)          # [image | pos | neg]
+        c.check(c.lib.var_ithor_encoder_fwd(c.handle, stream, ptr(flat), ptr(image), int(image.dtype == torch.uint8),
+                                            image.stride(0), ptr(pos), ptr(neg), B, m.config.img_dim[1], ptr(emb[0]),
+                                            ptr(emb[1]), ptr(emb[2]), None, None, 1), "var_ithor_encoder_fwd")
+        local = emb[1:].reshape(2 * B, 3)
+        lcls = torch.cat([gt, sn]) if mode else None
+        cand, ccls = local, lcls
+        if rccl is not None and world > 1:
+            cand = rccl.allgather(local.reshape(-1)).view(-1, 3)
+            if mode:
+                ccls = rccl.allgather(lcls.view(torch.float32)).view(torch.int32)      # (4-byte words: the classes' bits)
+        elif world > 1:
+            cand = torch.empty((world * 2 * B, 3), dtype=torch.float32, device=dev)
+            torch.distributed.all_gather_into_tensor(cand, local, group=self.pg)
+            if mode:
+                ccls = torch.empty(world * 2 * B, dtype=torch.int32, device=dev)
+                torch.distributed.all_gather_into_tensor(ccls, lcls, group=self.pg)
+        target = torch.arange(B, dtype=torch.int32, device=dev) + rank * 2 * B
+        loss, ga, gc = inbatch_contrastive_loss(emb[0], cand, target, tau, 1.0 / (B * world), gt if mode else None, ccls,
+                                                negatives if mode else "all")
+        if rccl is not None and world > 1:
+            rccl.allreduce(gc.view(-1))
+        elif world > 1:
+            torch.distributed.all_reduce(gc, op=torch.distributed.ReduceOp.SUM, group=self.pg)
+        mine = gc[rank * 2 * B:(rank + 1) * 2 * B]
+        c.check(c.lib.var_ithor_encoder_bwd(c.handle, stream, ptr(flat), ptr(ga), ptr(mine[:B]), ptr(mine[B:]), ptr(self.gbuf)),
+                "var_ithor_encoder_bwd")
+        self.gbuf[self.n:].copy_(loss)
+        self._keep = (image, pos, neg)
+        self.allreduce()
+        self.adam()
+        return self.loss
+
     def set_lr(self, lr):
         self.lr = lr
         if getattr(self, "_g_lr", None) is not None:

@@ -80,19 +80,55 @@ def mfcc_psf(pcm, lens=None, out_frames=600, clip_index=None):
     return out
 
 
-def inbatch_contrastive_loss(anchor, cand, target, tau=0.1, inv_count=None):
+INBATCH_NEGATIVES = {"all": 0, "other_class": 1, "multi_positive": 2}       # VAR_INBATCH_* of include/var_hip.h
+
+
+def inbatch_mode(negatives, have_classes):
+    """The head's mode for `negatives`; the class-aware ones need classes."""
+    if negatives not in INBATCH_NEGATIVES:
+        raise VarHipError(f"negatives is one of {sorted(INBATCH_NEGATIVES)}: got {negatives!r}")
+    if negatives != "all" and not have_classes:
+        raise VarHipError(f"negatives={negatives!r} needs the classes of the anchors and the candidates")
+    return INBATCH_NEGATIVES[negatives]
+
+
+def check_classes(t, n, device, what):
+    """A class table as the head reads it: `n` contiguous int32 entries on `device` (no silent conversion: a table of another
+    dtype or device is a caller's mistake, and a copy per step would hide it)."""
+    if not torch.is_tensor(t) or t.dtype != torch.int32 or t.device != device or t.numel() != n or not t.is_contiguous():
+        raise VarHipError(f"{what} must be a contiguous int32 tensor of {n} entries on {device}")
+    return t
+
+
+def inbatch_contrastive_loss(anchor, cand, target, tau=0.1, inv_count=None, anchor_cls=None, cand_cls=None, negatives="all"):
     """In-batch-negatives contrastive head (csrc/inbatch.hip; an extension of the reference's triplet loss, BASELINE
     config 3): anchor (B,3), cand (M,3) = every candidate sound embedding of the global batch, target (B) int32 =
-    column of each sample's positive.  Returns (loss[1], g_anchor (B,3), g_cand (M,3)); g_cand is this rank's partial."""
+    column of each sample's positive.  Returns (loss[1], g_anchor (B,3), g_cand (M,3)); g_cand is this rank's partial.
+    negatives: "all" scores every other candidate as a negative; with anchor_cls (B) / cand_cls (M) int32, "other_class"
+    leaves the other candidates of the anchor's class out and "multi_positive" counts them as positives
+    (include/var_hip.h: var_inbatch_loss_fwd_bwd_ex)."""
     _require_cuda(anchor, cand, target)
     a, cnd = anchor.contiguous().float(), cand.contiguous().float()
     t = target.to(torch.int32).contiguous()
     B, M = a.shape[0], cnd.shape[0]
+    have = anchor_cls is not None or cand_cls is not None
+    mode = inbatch_mode(negatives, have)
+    if have:
+        if anchor_cls is None or cand_cls is None:
+            raise VarHipError("anchor_cls and cand_cls come together")
+        check_classes(anchor_cls, B, a.device, "anchor_cls")
+        check_classes(cand_cls, M, a.device, "cand_cls")
     ctx = Context.get(a.device.index)
     loss = torch.empty(1, dtype=torch.float32, device=a.device)
     ga, gc = torch.empty_like(a), torch.empty_like(cnd)
-    scratch = torch.empty(2 * B, dtype=torch.float32, device=a.device)
-    ctx.check(ctx.lib.var_inbatch_loss_fwd_bwd(ctx.handle, current_stream_handle(), ptr(a), ptr(cnd), ptr(t), B, M, float(tau),
-                                               float(1.0 / B if inv_count is None else inv_count), ptr(scratch), ptr(loss),
-                                               ptr(ga), ptr(gc)), "var_inbatch_loss_fwd_bwd")
+    inv = float(1.0 / B if inv_count is None else inv_count)
+    if mode == 0:
+        scratch = torch.empty(2 * B, dtype=torch.float32, device=a.device)
+        ctx.check(ctx.lib.var_inbatch_loss_fwd_bwd(ctx.handle, current_stream_handle(), ptr(a), ptr(cnd), ptr(t), B, M, float(tau),
+                                                   inv, ptr(scratch), ptr(loss), ptr(ga), ptr(gc)), "var_inbatch_loss_fwd_bwd")
+        return loss, ga, gc
+    scratch = torch.empty(3 * B, dtype=torch.float32, device=a.device)
+    ctx.check(ctx.lib.var_inbatch_loss_fwd_bwd_ex(ctx.handle, current_stream_handle(), ptr(a), ptr(cnd), ptr(t), ptr(anchor_cls),
+                                                  ptr(cand_cls), B, M, float(tau), inv, mode, ptr(scratch), ptr(loss), ptr(ga),
+                                                  ptr(gc)), "var_inbatch_loss_fwd_bwd_ex")
     return loss, ga, gc

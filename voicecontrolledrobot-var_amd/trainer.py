@@ -12,6 +12,7 @@ import torch
 
 from ._lib import Context, VarHipError, ptr
 from .layout import N_PARAMS
+from .ops import check_classes, inbatch_mode
 from .ops import mfcc as mfcc_op  # noqa: F401
 
 
@@ -518,27 +519,51 @@ class VARTrainer:
         self.adam()
         return self.loss
 
-    def _inbatch_head(self, anchor, cand, target, tau, inv_count):
+    def _inbatch_head(self, anchor, cand, target, tau, inv_count, acls=None, ccls=None, mode=0):
         c = self.ctx
         B, M = anchor.shape[0], cand.shape[0]
         loss = torch.empty(1, dtype=torch.float32, device=self.dev)
         ga, gc = torch.empty_like(anchor), torch.empty_like(cand)
-        scratch = torch.empty(2 * B, dtype=torch.float32, device=self.dev)
-        c.check(c.lib.var_inbatch_loss_fwd_bwd(c.handle, c.stream(), ptr(anchor), ptr(cand), ptr(target), B, M, float(tau),
-                                               float(inv_count), ptr(scratch), ptr(loss), ptr(ga), ptr(gc)),
-                "var_inbatch_loss_fwd_bwd")
+        scratch = torch.empty(3 * B, dtype=torch.float32, device=self.dev)
+        if mode == 0:
+            c.check(c.lib.var_inbatch_loss_fwd_bwd(c.handle, c.stream(), ptr(anchor), ptr(cand), ptr(target), B, M, float(tau),
+                                                   float(inv_count), ptr(scratch), ptr(loss), ptr(ga), ptr(gc)),
+                    "var_inbatch_loss_fwd_bwd")
+        else:
+            c.check(c.lib.var_inbatch_loss_fwd_bwd_ex(c.handle, c.stream(), ptr(anchor), ptr(cand), ptr(target), ptr(acls),
+                                                      ptr(ccls), B, M, float(tau), float(inv_count), int(mode), ptr(scratch),
+                                                      ptr(loss), ptr(ga), ptr(gc)), "var_inbatch_loss_fwd_bwd_ex")
         return loss, ga, gc
 
-    def step_inbatch(self, image, pos, neg, tau=0.1):
+    def _gather_classes(self, local, out=None):
+        """Every rank's local candidate classes [gt ; sn] (int32), all-gathered exactly as the candidate embeddings are."""
+        if self.world <= 1:
+            return local
+        if self.rccl is not None:                            # (the C ABI gathers 4-byte words: the bits of the int32 classes)
+            got = self.rccl.allgather(local.view(torch.float32)).view(torch.int32)
+            return got if out is None else out.copy_(got)
+        if out is None:
+            out = torch.empty(self.world * local.numel(), dtype=torch.int32, device=self.dev)
+        torch.distributed.all_gather_into_tensor(out, local, group=self.pg)
+        return out
+
+    def step_inbatch(self, image, pos, neg, tau=0.1, classes=None, negatives="all"):
         """One optimisation step with the in-batch-negatives contrastive head instead of the triplet loss (BASELINE
         config 3; an extension, csrc/inbatch.hip): every rank's [positive ; negative] sound embeddings are all-gathered
         (6 KB per rank at B = 256), each rank scores its images against all of them, the candidate gradients are summed
         with one small all-reduce and each rank back-propagates its own rows; then the usual gradient all-reduce + Adam.
-        Collectives go through torch.distributed, or through the C ABI when use_rccl() was called.  Equal shards."""
+        Collectives go through torch.distributed, or through the C ABI when use_rccl() was called.  Equal shards.
+        classes = (gt (B), sn (B)) int32: the classes of this rank's positive and negative clips, for negatives =
+        "other_class" (the other candidates of an anchor's class are no negatives) or "multi_positive" (they are positives;
+        include/var_hip.h: var_inbatch_loss_fwd_bwd_ex).  The local candidate classes [gt ; sn] are all-gathered like the
+        embeddings (one more small all-gather); the anchors' classes are the rank's own gt.  "all" ignores the classes."""
         self._check(image, pos, neg)
         c, m = self.ctx, self.model
         flat = m.flat_parameters()
         B = image.shape[0]
+        mode = inbatch_mode(negatives, classes is not None)
+        if classes is not None:
+            gt, sn = (check_classes(t, B, self.dev, "classes = (gt, sn): each") for t in classes)
         c.ensure_plan(B, self.hw)
         dev = self.dev
         rccl, rank, world = self.rccl, self.rank, self.world
@@ -557,7 +582,10 @@ class VARTrainer:
         else:
             cand = local
         target = torch.arange(B, dtype=torch.int32, device=dev) + rank * 2 * B
-        loss, ga, gc = self._inbatch_head(emb[0], cand.contiguous(), target, tau, 1.0 / (B * world))
+        acls = ccls = None
+        if mode:
+            acls, ccls = gt, self._gather_classes(torch.cat([gt, sn]))
+        loss, ga, gc = self._inbatch_head(emb[0], cand.contiguous(), target, tau, 1.0 / (B * world), acls, ccls, mode)
         if rccl is not None and world > 1:
             rccl.allreduce(gc.view(-1))
         elif world > 1:
@@ -570,14 +598,21 @@ class VARTrainer:
         self.adam()
         return self.loss
 
-    def capture_inbatch_epoch_steps(self, images, pcm, batch, table, tau=0.1, clip_len=None):
+    def capture_inbatch_epoch_steps(self, images, pcm, batch, table, tau=0.1, clip_len=None, classes=None, negatives="all"):
         """step_inbatch as a replayed step over the HBM-resident dataset (BASELINE configs[2]): per step the captured
         graphs gather the images of the current index row, run the MFCC front-end, the encoder forward, the
         in-batch-negatives head, the encoder backward and Adam + row fetch.  With one rank everything is ONE graph; with
         several the three collectives (all-gather of the candidates, all-reduce of the candidate gradients, all-reduce
         of the parameter gradients) stay eager between four graphs.  Returns (replay, load_table) like
-        capture_epoch_steps; `table` rows are [image_index | clip_index (2B) | lens (2B)], equal shards."""
+        capture_epoch_steps; `table` rows are [image_index | clip_index (2B) | lens (2B)], equal shards.
+        classes = the WHOLE pool's (gt (N), sn (N)) int32 tables (TripletPool.class_tables) with negatives = "other_class" |
+        "multi_positive": the captured forward gathers the step's rows of them by the index row it already holds (two more
+        small launches, no host read); with several ranks their all-gather sits beside the candidates'."""
         B = batch
+        mode = inbatch_mode(negatives, classes is not None)
+        if classes is not None:
+            n_items = int(images.shape[0])
+            gt_tab, sn_tab = (check_classes(t, n_items, self.dev, "classes = the pool's (gt, sn): each") for t in classes)
         rows, row_ints = int(table.shape[0]), int(table.shape[1])
         if row_ints != 5 * B or table.dtype != torch.int32 or table.device != self.dev or not table.is_contiguous():
             raise VarHipError("index table must be a contiguous int32 (rows, 5*batch) tensor on the trainer's device")
@@ -596,14 +631,19 @@ class VARTrainer:
         target = (torch.arange(B, dtype=torch.int32, device=dev) + rank * 2 * B).contiguous()
         loss1 = torch.zeros(1, dtype=torch.float32, device=dev)
         ga, gc = torch.zeros((B, 3), dtype=torch.float32, device=dev), torch.zeros_like(cand)
-        scratch = torch.zeros(2 * B, dtype=torch.float32, device=dev)
+        scratch = torch.zeros(3 * B, dtype=torch.float32, device=dev)
         mine = gc[rank * 2 * B:(rank + 1) * 2 * B]
         clip_idx, lens = self._g_idx[B:3 * B], self._g_idx[3 * B:5 * B]
-        self._keep_inbatch = (img, feats, emb, cand, target, loss1, ga, gc, scratch)
+        lcls = torch.zeros(2 * B, dtype=torch.int32, device=dev)                 # this rank's [gt ; sn] of the step
+        ccls = torch.zeros(world * 2 * B, dtype=torch.int32, device=dev) if world > 1 else lcls
+        self._keep_inbatch = (img, feats, emb, cand, target, loss1, ga, gc, scratch, lcls, ccls)
 
         def body_fwd():
             self._bind()
             torch.index_select(images, 0, self._g_idx[:B], out=img)     # (int32 indices: no widening launch in front)
+            if mode:                                                    # (kernels too, not memcpy nodes: _lib.new_graph)
+                torch.index_select(gt_tab, 0, self._g_idx[:B], out=lcls[:B])
+                torch.index_select(sn_tab, 0, self._g_idx[:B], out=lcls[B:])
             with self._clips_bound(cache):
                 c.check(c.lib.var_mfcc(c.handle, c.stream(), ptr(pcm), ptr(lens), ptr(clip_idx), 2 * B, pcm.stride(0), 100,
                                        ptr(feats)), "var_mfcc")
@@ -612,6 +652,12 @@ class VARTrainer:
                                               ptr(emb[2]), None, None, 1), "var_arm_encoder_fwd")
 
         def body_loss():
+            if mode:
+                c.check(c.lib.var_inbatch_loss_fwd_bwd_ex(c.handle, c.stream(), ptr(emb[0]), ptr(cand), ptr(target), ptr(lcls),
+                                                          ptr(ccls), B, cand.shape[0], float(tau), 1.0 / (B * world), mode,
+                                                          ptr(scratch), ptr(loss1), ptr(ga), ptr(gc)),
+                        "var_inbatch_loss_fwd_bwd_ex")
+                return
             c.check(c.lib.var_inbatch_loss_fwd_bwd(c.handle, c.stream(), ptr(emb[0]), ptr(cand), ptr(target), B, cand.shape[0],
                                                    float(tau), 1.0 / (B * world), ptr(scratch), ptr(loss1), ptr(ga), ptr(gc)),
                     "var_inbatch_loss_fwd_bwd")
@@ -647,6 +693,8 @@ class VARTrainer:
                     cand.copy_(rccl.allgather(local.reshape(-1)).view(-1, 3))
                 else:
                     torch.distributed.all_gather_into_tensor(cand, local, group=self.pg)
+                if mode:
+                    self._gather_classes(lcls, out=ccls)
                 g_loss()
                 if rccl is not None:
                     rccl.allreduce(gc.view(-1))
@@ -746,7 +794,7 @@ def train_representation(model, batches, epochs, lr=1e-4, weight_decay=1e-6, mil
 
 def train_representation_from_pool(model, pool, epochs, batch, lr=1e-4, weight_decay=1e-6, milestones=None,
                                    gamma=0.2, margin=1.0, save_dir=None, save_interval=10, start_ep=0, log=print,
-                                   drop_last=False, _ctx=None):
+                                   drop_last=False, _ctx=None, head="triplet", tau=0.1, negatives="all"):
     """The loop of VAR/pretext_VAR.py:44-91 over a TripletPool resident in HBM (u8 images, int16 clips, frozen pairs =
     VARFineTuneDataset, dataset.py:94-133): every epoch is a freshly shuffled index table (DataLoader(shuffle=True),
     drop_last=False incl. the short last batch) walked by the replayed step -- gather, MFCC front-end, forward, triplet
@@ -755,9 +803,21 @@ def train_representation_from_pool(model, pool, epochs, batch, lr=1e-4, weight_d
     checkpoints every `save_interval` epochs and at the end (:75-80), progress.csv (:87-91).
     Both models: the Kuka one (1 s clips, torchaudio-flavour MFCC, milestones [10, 30, 50]) and the iTHOR one (clips of up
     to 6 s, python_speech_features MFCC of 600 frames, milestones [20, 30] -- its reference default of 500 triplets at batch
-    128 runs as 128 / 128 / 128 / 116, Envs/ai2thor/config.py:24,41-48)."""
+    128 runs as 128 / 128 / 128 / 116, Envs/ai2thor/config.py:24,41-48).
+    head="inbatch" (an extension, Kuka model only): the in-batch-negatives head at temperature `tau` instead of the triplet
+    loss, walked by capture_inbatch_epoch_steps with the pool's class tables; negatives = "all" | "other_class" |
+    "multi_positive" says what the candidates of an anchor's own class are.  Equal batches: batch divides the pool, or
+    drop_last=True."""
     from .ithor import IthorTrainer, IthorVARPretextNet
     is_ithor = isinstance(model, IthorVARPretextNet)
+    if head not in ("triplet", "inbatch"):
+        raise VarHipError(f"head is 'triplet' or 'inbatch': got {head!r}")
+    inbatch_mode(negatives, True)
+    if head == "inbatch" and is_ithor:
+        raise VarHipError("head='inbatch' replays the Kuka model's captured in-batch step; the iTHOR model has the eager "
+                          "IthorTrainer.step_inbatch only (no captured iTHOR in-batch step)")
+    if head == "triplet" and negatives != "all":
+        raise VarHipError("negatives applies to head='inbatch': the triplet loss draws its negatives itself")
     if milestones is None:
         milestones = (20, 30) if is_ithor else (10, 30, 50)
     if is_ithor:
@@ -768,6 +828,9 @@ def train_representation_from_pool(model, pool, epochs, batch, lr=1e-4, weight_d
         pool.freeze_pairs()
     model.train()
     spe, bt = pool.steps_per_epoch(batch, drop_last), pool.tail_batch(batch, drop_last)
+    if head == "inbatch" and bt:
+        raise VarHipError(f"head='inbatch' runs equal batches: batch {batch} does not divide the pool's {pool.n_items} "
+                          "triplets (pass drop_last=True)")
     if spe < 1:
         raise VarHipError(f"the pool holds {pool.n_items} triplets: no step of batch {batch} with drop_last={drop_last}")
     replay = load_table = None
@@ -778,7 +841,11 @@ def train_representation_from_pool(model, pool, epochs, batch, lr=1e-4, weight_d
     for ep in range(epochs):
         tr.set_lr(multistep_lr(lr, milestones, gamma, ep))
         table = pool.epoch_index_table(batch, drop_last)
-        if replay is None:
+        if replay is None and head == "inbatch":
+            replay, load_table = tr.capture_inbatch_epoch_steps(pool.images, pool.clips, batch, table, tau=tau,
+                                                                clip_len=pool.clip_len, classes=pool.class_tables(),
+                                                                negatives=negatives)
+        elif replay is None:
             kw = {} if is_ithor else {"clip_len": pool.clip_len}
             replay, load_table = tr.capture_epoch_steps(pool.images, pool.clips, batch, table, steps_per_epoch=spe,
                                                         tail_batch=bt, **kw)
